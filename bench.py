@@ -8,11 +8,18 @@ by mdemi.train.build_from_config (the restated run.py construction): SILog
 alpha 10 / beta 0.15, AdamW lr 2e-5 wd 0 with OneCycle, grad_norm 0.1.
 A step = forward + loss + backward + (N > 1: bucketed RCCL gradient all-reduce
 overlapped with the backward) + clipped AdamW update + scheduler step, all on
-libmdemi kernels; synthetic inputs.  The same line carries a
-secondary measurement at the north_star shape (NeW-CRFs KITTI 352x1216, bs 8/GPU;
-BASELINE configs[2], and configs[3] when N = 8).
+libmdemi kernels; synthetic inputs.
+
+A plain run does only what the headline figure needs: build, W warm-up steps, K
+timed steps, the result line.  --full adds every other measurement to the same
+line: the instrumented roofline step, the CPU baselines, the secondary workloads
+(among them the north_star shape, NeW-CRFs KITTI 352x1216, bs 8/GPU; BASELINE
+configs[2], and configs[3] when N = 8), configs[0], and with a process group the
+isolated gradient exchange and its overlap trace.  --dump-outputs DIR writes what
+the last timed step returned and left behind (dump_outputs) as DIR/<name>.npy.
 
   python bench.py [--gpus N --steps K --warmup W]        (N > 1: starts N ranks itself)
+  python bench.py --full ...                             (every measurement)
   torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
   python bench.py --config json/kitti/adabins/adabins_cham_per_batch_4gpu.json
 
@@ -114,7 +121,7 @@ WORKLOADS = {
                  workload="ODA2 ordered-swin2 (Swin-L) train step, KITTI 352x704",
                  ref_cfg="json/kitti/oda2/oda2_red_order_swin2.json"),
 }
-# The default line (BASELINE.json metric, NeW-CRFs NYU) carries every other single-GPU
+# With --full the default line (BASELINE.json metric, NeW-CRFs NYU) carries every other single-GPU
 # BASELINE config as a compact secondary: configs[2] (NeW-CRFs KITTI 352x1216 bs 8),
 # configs[1] (AdaBins NYU bs 16) and configs[4] at N GPUs (Depthformer v8 bf16 + hipGraph).
 SECONDARIES = {"newcrfs_kitti": 8, "newcrfs_kitti704": 8, "adabins": 16, "depthformer_bf16": 8}
@@ -136,6 +143,13 @@ def parse():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the instrumented roofline step, the CPU "
+                         "baselines, the secondary workloads and configs[0], the isolated gradient exchange "
+                         "(each can still be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned and left behind (loss, seeded "
+                         "samples of the parameters and AdamW moments) as DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=20.0)
     ap.add_argument("--no-roofline", action="store_true")
@@ -158,7 +172,12 @@ def parse():
                          "buckets and their all-reduces (the N > 1 code path on one GPU)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: launcher/gloo plumbing check only (a toy model, not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline's build, warm-up and timed steps only
+        args.no_cpu_baseline = args.no_roofline = args.no_secondary = True
+    return args
 
 
 # --------------------------------------------------------------------------- launcher
@@ -661,9 +680,50 @@ def cpu_baseline(model, opt, H, W, budget_s, all_cores=True):
     return res
 
 
+# --------------------------------------------------------------------------- outputs
+DUMP_SAMPLE_ELEMS = 2_000_000  # elements per sampled array: 3 arrays x 4 B stay far below 64 MB
+DUMP_SAMPLE_MIN = 16  # every parameter tensor contributes at least this many elements
+DUMP_SEED = 20611
+
+
+def dump_outputs(path, trainer, loss):
+    """--dump-outputs: what the last timed Trainer.step handed its caller, as float32
+    path/<name>.npy -- the loss it returned (loss.npy, one element) and the state it left
+    behind: the parameters (params.npy) and the AdamW moments (exp_avg.npy, exp_avg_sq.npy;
+    the first moment is the running mean of the clipped gradients, so it moves with every
+    backward kernel).  The three state arrays are the same fixed sample: parameter tensors in
+    param_groups order, from each a share of DUMP_SAMPLE_ELEMS proportional to its size (at
+    least DUMP_SAMPLE_MIN, whole when it has no more) at flat indices drawn once from a CPU
+    generator seeded with DUMP_SEED, so two builds run with the same arguments write
+    element-for-element comparable files.  A parameter without state yet dumps zeros."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p for g in trainer.optimizer.param_groups for p in g["params"]]
+    frac = min(1.0, DUMP_SAMPLE_ELEMS / max(1, sum(p.numel() for p in params)))
+    gen = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    cols = {"params": [], "exp_avg": [], "exp_avg_sq": []}
+    with torch.no_grad():
+        for p in params:
+            n = p.numel()
+            k = min(n, max(DUMP_SAMPLE_MIN, int(n * frac)))
+            idx = (torch.arange(n) if k == n else torch.randint(0, n, (k,), generator=gen)).to(p.device)
+            st = trainer.optimizer.state.get(p) or {}
+            for name, t in (("params", p), ("exp_avg", st.get("exp_avg")), ("exp_avg_sq", st.get("exp_avg_sq"))):
+                cols[name].append(torch.zeros(k, device=p.device) if t is None else
+                                  t.detach().reshape(-1)[idx].float())
+        arrays = {name: torch.cat(v).cpu().numpy() for name, v in cols.items()}
+        arrays["loss"] = loss.detach().float().reshape(-1).cpu().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32, copy=False))
+
+
 # --------------------------------------------------------------------------- one measurement
-def measure(args, opt, key, H, W, B, rank, world, device, with_roofline, precision="fp32", graph=False):
-    """Build the trainer from `opt`, run W warm-up + K timed steps; returns a dict."""
+def measure(args, opt, key, H, W, B, rank, world, device, with_roofline, precision="fp32", graph=False,
+            dump_dir=None):
+    """Build the trainer from `opt`, run W warm-up + K timed steps; returns a dict.
+    dump_dir: write the last timed step's outputs there (dump_outputs; rank 0), before
+    any further instrumented step moves the state."""
     from mdemi.train import build_from_config
     opt = copy.deepcopy(opt)
     opt["dataloader"]["batch_size"] = B
@@ -699,7 +759,10 @@ def measure(args, opt, key, H, W, B, rank, world, device, with_roofline, precisi
            "loss": float(loss.item()), "num_accum": na, "trainer": trainer,
            # peak device memory of the build + warm-up + timed steps (bf16 storage: incl. the copies)
            "peak_mem_GB": round(torch.cuda.max_memory_allocated(device) / 1e9, 2)}
-    if trainer.ddp is not None:  # isolated cost of the whole gradient exchange (no overlap): an upper bound on exposed comm
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, trainer, loss)
+        _progress(f"{key}: outputs written to {dump_dir}")
+    if trainer.ddp is not None and args.full:  # isolated cost of the whole gradient exchange (no overlap): an upper bound on exposed comm
         ddp = trainer.ddp
         torch.cuda.synchronize()
         dist.barrier()
@@ -958,7 +1021,7 @@ def main():
     graph = args.graph or wl.get("graph", False)  # data parallel too: the RCCL all-reduces are in the graph
 
     res = measure(args, opt, key, H, W, B, rank, world, device, with_roofline=not args.no_roofline,
-                  precision=precision, graph=graph)
+                  precision=precision, graph=graph, dump_dir=args.dump_outputs)
     value = res["images"] / res["elapsed"]
     files = None
     if pipe is not None:

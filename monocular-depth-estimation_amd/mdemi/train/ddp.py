@@ -76,7 +76,7 @@ class GradAllReduce:
         self._sync = True
         # trace_events: record a HIP event on the compute stream when each bucket becomes ready
         # (its last gradient landed) and when it is launched, and one at the end of backward
-        # (finish) -- bench.py --ddp reports the offsets (eager steps only, never in a capture)
+        # (finish) -- bench.py --full --ddp reports the offsets (eager steps only, never in a capture)
         self.trace_events = False
         self.trace = None
         self._handles = [p.register_post_accumulate_grad_hook(self._hook) for p in self.params]

@@ -98,8 +98,8 @@ def test_graph_captured_ddp_step_matches_eager(rccl, num_accum):
 
 
 def test_bucket_readiness_trace(rccl):
-    """the traced step (GradAllReduce.trace_events, bench.py --ddp's
-    `allreduce.overlap`) records when each bucket became ready and was launched; buckets
+    """the traced step (GradAllReduce.trace_events, bench.py --full
+    --ddp's `allreduce.overlap`) records when each bucket became ready and was launched; buckets
     launch in index order, each no earlier than it was ready, the first ones well before the
     end of backward; after the first step's bucket rebuild they also become ready in index
     order; the trace is off again afterwards and leaves the step's results alone."""

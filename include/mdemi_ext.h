@@ -180,6 +180,27 @@ int mdemi_flip_w(const float* x, float* y, int64_t rows, int32_t W, void* stream
 int mdemi_flip_avg_w(const float* a, const float* b, float* y, int64_t rows, int32_t W, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Prediction export (utils/visualize_utils.py:10-29 colorize, :32-51        */
+/* visualization): one launch reads pred [B][h][w] once and writes every     */
+/* non-NULL output once, each [B][H][W] (rgba: x4 bytes).  (h, w) != (H, W)  */
+/* resamples with the align_corners=True taps of mdemi_bilinear_fwd.         */
+/*   depth_out: the (resampled) fp32 depth d                                 */
+/*   rgba: colorize(d, vmin, vmax) through lut (256 x RGBA8, device): all    */
+/*     in fp32, x = (d - vmin) / (vmax - vmin) (the range formed in double   */
+/*     from the two floats, rounded once; x = d * 0 when vmin == vmax),      */
+/*     index = trunc(x * 256) with 256 -> 255; NaN -> (0,0,0,0); d > vmax or */
+/*     d < vmin (+-inf included) -> (255,255,255,255)                        */
+/*   raw16: min(65535, rint(d * png_scale)) (round half even), 0 for NaN and */
+/*     d <= 0: the 16-bit depth PNG payload, png_scale 256 (KITTI) / 1000    */
+/*     (NYU), so that png / png_scale reads back within 0.5 / png_scale      */
+/* rgba and lut 4-byte aligned; 16-byte aligned pred / depth_out / rgba and  */
+/* 8-byte aligned raw16 take the 4-pixel vector path.                        */
+/* ------------------------------------------------------------------------ */
+int mdemi_depth_export(const float* pred, int32_t B, int32_t h, int32_t w, int32_t H, int32_t W, float vmin,
+                       float vmax, const uint8_t* lut, float png_scale, float* depth_out, uint8_t* rgba,
+                       uint16_t* raw16, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* AdaBins bin-centre chamfer loss (cfg loss.chamfer_weight; upstream        */
 /* BinsChamferLoss over pytorch3d chamfer_distance -- the reference's loss  */
 /* module is absent, parity unpinned).  from_edges: edges [B][P+1] (AdaBins) */

@@ -10,33 +10,9 @@
 //  - PixelShuffle as an NHWC index map (NewCRFDepth.py:132-136)
 //  - patchify for stride==kernel convs (swin_transformer.py:420-436)
 //  - NCHW <-> NHWC at the model boundary
-#include "common.h"
+#include "bilinear.h"  // Axis, make_axis, bilerp (shared with export.hip)
 
 namespace mdemi {
-
-struct Axis {
-  int in, out, align;
-  float scale;  // ATen rheight/rwidth
-  __device__ __forceinline__ void tap(int o, int& i0, int& ip, float& l1) const {
-    float src;
-    if (align) src = scale * (float)o;
-    else {
-      src = scale * ((float)o + 0.5f) - 0.5f;
-      src = src < 0.f ? 0.f : src;
-    }
-    i0 = (int)src;
-    ip = (i0 < in - 1) ? 1 : 0;
-    l1 = src - (float)i0;
-  }
-};
-
-static Axis make_axis(int in, int out, int align, float user_scale) {
-  Axis a;
-  a.in = in; a.out = out; a.align = align;
-  if (align) a.scale = out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f;
-  else a.scale = user_scale > 0.f ? 1.f / user_scale : (float)in / (float)out;
-  return a;
-}
 
 template <int VEC>
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int N,
@@ -63,13 +39,13 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restri
       const float4 a = *reinterpret_cast<const float4*>(p00), b = *reinterpret_cast<const float4*>(p01);
       const float4 c = *reinterpret_cast<const float4*>(p10), d = *reinterpret_cast<const float4*>(p11);
       float4 o;
-      o.x = hl0 * (wl0 * a.x + wl1 * b.x) + hl1 * (wl0 * c.x + wl1 * d.x);
-      o.y = hl0 * (wl0 * a.y + wl1 * b.y) + hl1 * (wl0 * c.y + wl1 * d.y);
-      o.z = hl0 * (wl0 * a.z + wl1 * b.z) + hl1 * (wl0 * c.z + wl1 * d.z);
-      o.w = hl0 * (wl0 * a.w + wl1 * b.w) + hl1 * (wl0 * c.w + wl1 * d.w);
+      o.x = bilerp(hl0, hl1, wl0, wl1, a.x, b.x, c.x, d.x);
+      o.y = bilerp(hl0, hl1, wl0, wl1, a.y, b.y, c.y, d.y);
+      o.z = bilerp(hl0, hl1, wl0, wl1, a.z, b.z, c.z, d.z);
+      o.w = bilerp(hl0, hl1, wl0, wl1, a.w, b.w, c.w, d.w);
       *reinterpret_cast<float4*>(dst) = o;
     } else {
-      dst[0] = hl0 * (wl0 * p00[0] + wl1 * p01[0]) + hl1 * (wl0 * p10[0] + wl1 * p11[0]);
+      dst[0] = bilerp(hl0, hl1, wl0, wl1, p00[0], p01[0], p10[0], p11[0]);
     }
   }
 }

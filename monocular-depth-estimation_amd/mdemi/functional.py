@@ -1963,6 +1963,54 @@ def flip_avg_w(a, b):
     return y
 
 
+EXPORT_OUTPUTS = ("depth", "rgba", "raw16")
+
+
+def depth_export(pred, size=None, vmin=10, vmax=1000, lut=None, png_scale=None, outputs=EXPORT_OUTPUTS):
+    """Prediction export in one sweep (mdemi_depth_export): pred (B,1,h,w) or (B,h,w) fp32 ->
+    a dict with the requested ``outputs``:
+      "depth"  (B,1,H,W) fp32, pred resized to ``size`` (bilinear, align_corners=True) when it differs
+      "rgba"   (B,H,W,4) uint8, utils.visualize_utils.colorize of that depth between vmin and vmax;
+               ``lut`` is a colormap name (default the reference's 'magma_r') or a uint8 [256,4]
+               device tensor (utils.visualize_utils.colormap_lut)
+      "raw16"  (B,H,W) uint16, min(65535, rint(depth * png_scale)), 0 for NaN and depth <= 0:
+               the 16-bit PNG payload (png_scale 256 for KITTI, 1000 for NYU)
+    vmin / vmax default to the reference colorize's.  No autograd; launches on the current
+    stream and does not synchronise with the host."""
+    _require_cuda(pred)
+    outputs = tuple(outputs)
+    bad = [o for o in outputs if o not in EXPORT_OUTPUTS]
+    if bad or not outputs:
+        raise ValueError(f"depth_export: outputs must be a non-empty subset of {EXPORT_OUTPUTS}, got {outputs}")
+    if pred.dim() == 4 and pred.shape[1] == 1:
+        pred = pred[:, 0]
+    if pred.dim() != 3:
+        raise ValueError(f"depth_export: pred must be (B,1,h,w) or (B,h,w), got {tuple(pred.shape)}")
+    pred = _c(pred.detach())
+    B, h, w = pred.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    dev = pred.device
+    out = {}
+    if "depth" in outputs:
+        out["depth"] = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
+    if "rgba" in outputs:
+        if lut is None or isinstance(lut, str):
+            from .utils.visualize_utils import colormap_lut_device
+            lut = colormap_lut_device(lut or "magma_r", dev)
+        if lut.device != dev or lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 4) or not lut.is_contiguous():
+            raise ValueError("depth_export: lut must be a contiguous uint8 [256, 4] tensor on pred's device")
+        out["rgba"] = torch.empty(B, H, W, 4, device=dev, dtype=torch.uint8)
+    if "raw16" in outputs:
+        if png_scale is None:
+            raise ValueError("depth_export: raw16 needs png_scale (256 for KITTI, 1000 for NYU)")
+        out["raw16"] = torch.empty(B, H, W, device=dev, dtype=torch.uint16)
+    if B * H * W:
+        L.call("mdemi_depth_export", pred.data_ptr(), B, h, w, H, W, float(vmin), float(vmax),
+               lut.data_ptr() if "rgba" in outputs else None, float(png_scale or 0.0), L.ptr(out.get("depth")),
+               L.ptr(out.get("rgba")), L.ptr(out.get("raw16")), L.stream())
+    return out
+
+
 class _BinsChamferFn(torch.autograd.Function):
     """Bin-centre chamfer loss (upstream AdaBins BinsChamferLoss over pytorch3d chamfer_distance
     defaults; the reference's loss module is absent -- parity unpinned): batch mean of

@@ -305,6 +305,40 @@ int mdemi_glu_bwd(const float* x, const float* dy, float* dx, int64_t M, int32_t
 int mdemi_pad_replicate(const float* x, float* y, int32_t N, int32_t H, int32_t W, int32_t C, int32_t OH,
                         int32_t OW, int32_t pt, int32_t pl, int32_t inverse, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Step telemetry for the training driver (mdemi.run / mdemi.train.loop)     */
+/* ------------------------------------------------------------------------ */
+/* sumsq[0] = sum_t ||param_t||^2 over a tensor table (the norm the reference */
+/* logged: utils/common_utils.py:65-75 compute_param_norm).  Same (tensor,   */
+/* chunk) item maps and workspace as mdemi_grad_sumsq                        */
+/* (mdemi_grad_norm_workspace_size): fp32 partial per item, fp64 final sum   */
+/* in a fixed order -- deterministic.  Only `param` and `numel` of each      */
+/* entry are read.                                                           */
+int mdemi_param_sumsq(const mdemi_tensor_ref* tensors_dev, int32_t ntensors, int64_t nitems, float* sumsq,
+                      void* workspace, void* stream);
+
+/* One record per optimizer step, appended on the device.                    */
+#define MDEMI_STEP_LOSS_NONFINITE 1u
+#define MDEMI_STEP_GRAD_NONFINITE 2u
+typedef struct mdemi_step_record {
+  float loss;
+  float grad_sumsq; /* ||grad_scale * grad||^2 before the clip; -1 when not given */
+  int32_t index;    /* 0-based push count */
+  uint32_t flags;   /* MDEMI_STEP_* */
+} mdemi_step_record;
+typedef struct mdemi_telemetry_state {
+  int32_t pushed;          /* records appended so far */
+  int32_t nonfinite_steps; /* records with a flag set */
+  int32_t first_nonfinite; /* index of the first of them; the host initialises -1 */
+  int32_t _pad;
+} mdemi_telemetry_state;
+/* A one-thread kernel: ring[state->pushed % capacity] = {loss[0], grad_sumsq */
+/* ? grad_sumsq[0] : -1, pushed, flags}, then the counters advance.  ring,   */
+/* state, loss and grad_sumsq (may be NULL) are device pointers; the counter */
+/* lives on the device, so a captured hipGraph advances it on every replay.  */
+int mdemi_telemetry_push(mdemi_step_record* ring, int32_t capacity, mdemi_telemetry_state* state,
+                         const float* loss, const float* grad_sumsq, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

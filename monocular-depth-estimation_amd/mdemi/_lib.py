@@ -98,6 +98,17 @@ class AdamWGroup(ctypes.Structure):
                 ("_pad", i32)]
 
 
+STEP_LOSS_NONFINITE, STEP_GRAD_NONFINITE = 1, 2  # include/mdemi_ext.h MDEMI_STEP_*
+
+
+class StepRecord(ctypes.Structure):  # include/mdemi_ext.h mdemi_step_record
+    _fields_ = [("loss", f32), ("grad_sumsq", f32), ("index", i32), ("flags", ctypes.c_uint32)]
+
+
+class TelemetryState(ctypes.Structure):  # include/mdemi_ext.h mdemi_telemetry_state
+    _fields_ = [("pushed", i32), ("nonfinite_steps", i32), ("first_nonfinite", i32), ("_pad", i32)]
+
+
 AUG_MAX_SPANS = 8  # include/mdemi_ext.h MDEMI_AUG_MAX_SPANS
 
 
@@ -230,6 +241,8 @@ _SIGS = {
     "mdemi_glu_fwd": (ctypes.c_int, [vp, vp, i64, i32, vp]),
     "mdemi_glu_bwd": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
     "mdemi_pad_replicate": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "mdemi_param_sumsq": (ctypes.c_int, [vp, i32, i64, vp, vp, vp]),
+    "mdemi_telemetry_push": (ctypes.c_int, [vp, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -228,9 +228,13 @@ class Trainer:
     Each call is exactly one optimizer step.  Dropout seeds are drawn on the GPU, so
     masks differ per replay."""
 
-    def __init__(self, opt, model, criterion, optimizer, scheduler, ddp=None, precision="fp32", graph=False):
+    def __init__(self, opt, model, criterion, optimizer, scheduler, ddp=None, precision="fp32", graph=False,
+                 telemetry=None):
         tr = opt.get("train", {})
         self.opt, self.model, self.criterion = opt, model, criterion
+        # train.telemetry.Telemetry (or None): one record per optimizer step, pushed on the
+        # step's stream right after the update -- inside the capture in graph mode
+        self.telemetry = telemetry
         self.optimizer, self.scheduler, self.ddp = optimizer, scheduler, ddp
         self.num_accum = int(tr.get("num_accum", 1))
         self.freeze_encoder_bn = bool(tr.get("freeze_encoder_bn", False))
@@ -334,6 +338,8 @@ class Trainer:
         if self.ddp is not None:
             self.ddp.finish()
         self.optimizer.step()
+        if self.telemetry is not None:
+            self.telemetry.push(total, self.optimizer)
         return total
 
     def save(self, prefix, save_dir, current_iter, best_value, best_epoch=None, best_iter=None, model_only=False):
@@ -380,12 +386,13 @@ class _null:
 
 
 def build_from_config(opt, device=None, world=1, steps_per_epoch=None, ddp_bucket_mb=64.0, drop_path=None,
-                      precision=None, graph=False, ddp=None):
+                      precision=None, graph=False, ddp=None, telemetry=None):
     """opt (parse()'s dict) -> Trainer.  device='meta' builds every object without
     allocating parameters (config validation); world > 1 (or ddp=True, e.g. a world-1
     RCCL group) wraps the gradients in the bucketed RCCL all-reduce (needs an
     initialised process group).  precision (default: train.precision or "fp32") and
-    graph select the mixed-precision / hipGraph-captured step (Trainer)."""
+    graph select the mixed-precision / hipGraph-captured step (Trainer); telemetry
+    (train.telemetry.Telemetry) records every step's loss and gradient norm on the device."""
     name = opt["model"]["name"]
     if device is not None and torch.device(device).type == "meta":
         with torch.device("meta"):
@@ -404,6 +411,7 @@ def build_from_config(opt, device=None, world=1, steps_per_epoch=None, ddp_bucke
         broadcast_parameters(model)
         grad_ar = GradAllReduce(model, bucket_mb=ddp_bucket_mb)
     precision = precision or opt.get("train", {}).get("precision", "fp32")
-    trainer = Trainer(opt, model, criterion, optimizer, scheduler, grad_ar, precision=precision, graph=graph)
+    trainer = Trainer(opt, model, criterion, optimizer, scheduler, grad_ar, precision=precision, graph=graph,
+                      telemetry=telemetry)
     trainer.train_mode()
     return trainer

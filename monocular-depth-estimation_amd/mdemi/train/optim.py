@@ -61,6 +61,7 @@ class FusedAdamW:
         self._steps_dev = None
         self._chunk = L.load().mdemi_multi_tensor_chunk()
         self._sumsq = None
+        self._psumsq = None  # param_norm()'s sum of squares
         self.capturable = bool(capturable)
         self._sched_rows = None  # host schedule [(lr, beta1, beta2, eps, wd) per group] per step
         self._sched_dev = None
@@ -220,6 +221,36 @@ class FusedAdamW:
                 _mf.set_b16(p, b16)
         if not capturing:  # a capture records the step; replays advance the mirrors (replayed())
             self.replayed()
+
+    # ---- step telemetry (train.loop) ----
+    def _table(self, what):
+        if self._tbl_key is None:
+            raise RuntimeError(f"FusedAdamW.{what}: no tensor table yet -- call it after a step()")
+        return self._tbl
+
+    def grad_sumsq_tensor(self):
+        """Device scalar holding this step's ||grad_scale * grad||^2 (before the clip), to be
+        called right after step() while the gradients are still in place.  With the clip on it
+        is the value step() already computed; with it off (max_grad_norm == 0) this launches
+        mdemi_grad_sumsq over the step's table.  Either way the tensor is the one persistent
+        ``_sumsq`` buffer: its address never changes, so the call can sit in a captured step."""
+        _, _, tl_ptr, ws_ptr, nt, ni, _ = self._table("grad_sumsq_tensor")
+        if not self.max_grad_norm > 0:
+            L.check(L.load().mdemi_grad_sumsq(tl_ptr, nt, ni, float(self.grad_scale), self._sumsq.data_ptr(), ws_ptr,
+                                              L.stream()), "grad_sumsq")
+        return self._sumsq
+
+    def param_norm(self):
+        """Device scalar: the 2-norm over the parameters of the current table
+        (mdemi_param_sumsq, deterministic).  The table holds the parameters that had a
+        gradient at the last step; the reference's compute_param_norm
+        (utils/common_utils.py:65-75) filters on requires_grad instead, so a trainable
+        parameter that never receives a gradient is counted there and not here."""
+        _, _, tl_ptr, ws_ptr, nt, ni, _ = self._table("param_norm")
+        if self._psumsq is None:
+            self._psumsq = torch.zeros(1, device=self._sumsq.device, dtype=torch.float32)
+        L.check(L.load().mdemi_param_sumsq(tl_ptr, nt, ni, self._psumsq.data_ptr(), ws_ptr, L.stream()), "param_sumsq")
+        return torch.sqrt(self._psumsq[0])
 
     def replayed(self):
         """Advance the host mirrors by one executed step over the current table's parameters."""

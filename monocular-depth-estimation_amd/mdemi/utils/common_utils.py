@@ -3,10 +3,14 @@ JSON configs unchanged (common_utils.py:34-52); gpu_ids select devices through
 HIP_VISIBLE_DEVICES (ROCm's CUDA_VISIBLE_DEVICES).  RunningAverage /
 RunningAverageDict (common_utils.py:92-135) accumulate the eval metrics.
 save_checkpoint (common_utils.py:12-31) writes the reference's training-state file;
-load_checkpoint reads one (the reference's or ours) back for a resume."""
+load_checkpoint reads one (the reference's or ours) back for a resume.  The driver's
+helpers (dprint, time_log, Timer, zero_grad_bn, compute_param_norm: common_utils.py:55-89,
+139-147) keep the reference's signatures."""
 import json
 import os
+import time
 from collections import OrderedDict
+from datetime import datetime
 
 import torch
 
@@ -71,6 +75,83 @@ def parse(json_path: str, write_option: bool = True) -> dict:
         with open(os.path.join(opt["output_dir"], "option.json"), "w", encoding="utf-8") as f:
             json.dump(opt, f, indent="\t")
     return opt
+
+
+def dprint(*args, local_rank: int = 0, **kwargs) -> None:
+    """common_utils.py:55-57: print on local rank 0 only."""
+    if local_rank == 0:
+        print(*args, **kwargs)
+
+
+def time_log() -> str:
+    """common_utils.py:60-62: a rule of 48 asterisks and the date / time, newline-terminated."""
+    now = datetime.now()
+    stamp = f"{now.year:>4}/{now.month:>2}/{now.day:>2} | {now.hour:>2}:{now.minute:>2}:{now.second:>2}"
+    return "*" * 48 + "  " + stamp + "\n"
+
+
+def _param_sumsq_gpu(params):
+    """sum ||p||^2 of contiguous fp32 CUDA tensors on one device through mdemi_param_sumsq."""
+    import ctypes
+    import math
+
+    from .. import _lib as L
+    lib = L.load()
+    chunk = lib.mdemi_multi_tensor_chunk()
+    refs, items_t, items_c = (L.TensorRef * len(params))(), [], []
+    for ti, p in enumerate(params):
+        refs[ti].param, refs[ti].numel = p.data_ptr(), p.numel()
+        nch = max(1, math.ceil(p.numel() / chunk))
+        items_t.extend([ti] * nch)
+        items_c.extend(range(nch))
+    ni = len(items_t)
+    dev = params[0].device
+    with torch.cuda.device(dev):
+        tbl = torch.frombuffer(bytearray(bytes(refs)), dtype=torch.uint8).to(dev)
+        ws = torch.zeros(lib.mdemi_grad_norm_workspace_size(ni) // 4, dtype=torch.int32)
+        ws[:2 * ni] = torch.tensor(items_t + items_c, dtype=torch.int32)
+        ws = ws.to(dev)
+        out = torch.zeros(1, dtype=torch.float32, device=dev)
+        L.check(lib.mdemi_param_sumsq(tbl.data_ptr(), len(params), ni, out.data_ptr(), ws.data_ptr(), L.stream()),
+                "param_sumsq")
+    return out[0]
+
+
+@torch.no_grad()
+def compute_param_norm(parameters, norm_type: float = 2.0) -> torch.Tensor:
+    """common_utils.py:65-75: the norm_type-norm of the per-parameter norm_type-norms over the
+    parameters with requires_grad, as a tensor on the first one's device (0. when there is
+    none).  The 2-norm of contiguous fp32 CUDA parameters on one device is one
+    mdemi_param_sumsq sweep; anything else is computed with torch."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.requires_grad]
+    if not params:
+        return torch.as_tensor(0.0, dtype=torch.float32)
+    dev = params[0].device
+    if (float(norm_type) == 2.0 and dev.type == "cuda"
+            and all(p.device == dev and p.dtype == torch.float32 and p.is_contiguous() for p in params)):
+        return torch.sqrt(_param_sumsq_gpu([p.detach() for p in params]))
+    return torch.norm(torch.stack([torch.norm(p.detach(), norm_type).to(dev) for p in params]), norm_type)
+
+
+def zero_grad_bn(model) -> None:
+    """common_utils.py:84-89: drop the gradients of every BatchNorm's parameters."""
+    for m in model.modules():
+        if isinstance(m, (torch.nn.BatchNorm1d, torch.nn.BatchNorm2d, torch.nn.SyncBatchNorm)):
+            for p in m.parameters():
+                p.grad = None
+
+
+class Timer:
+    """common_utils.py:139-147: update() returns the process CPU time since the last call, in ms."""
+
+    def __init__(self):
+        self._now = time.process_time_ns()
+
+    def update(self) -> float:
+        last, self._now = self._now, time.process_time_ns()
+        return (self._now - last) / 1e6
 
 
 class RunningAverage:

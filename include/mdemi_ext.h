@@ -339,6 +339,50 @@ typedef struct mdemi_telemetry_state {
 int mdemi_telemetry_push(mdemi_step_record* ring, int32_t capacity, mdemi_telemetry_state* state,
                          const float* loss, const float* grad_sumsq, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Guarded AdamW steps (train.nonfinite: "skip"): mdemi_adamw_step16 /       */
+/* mdemi_adamw_step_dev16 (mdemi.h) that drop a step with non-finite         */
+/* gradients on the device, with no host in the loop.                        */
+/*   ok = isfinite(sumsq[0])                                                 */
+/* sumsq is the scalar mdemi_grad_sumsq left over the SAME table and         */
+/* grad_scale; it is required here, also when max_norm == 0 (NULL gives      */
+/* MDEMI_EINVAL and nothing is launched).  Squares are non-negative and the  */
+/* final sum is fp64, so a NaN or inf in any gradient element reaches it and */
+/* nothing cancels it.  A finite gradient whose fp32 sum of squares          */
+/* overflows (an element beyond ~1.8e19, or a work item whose squares add up */
+/* to more than FLT_MAX) is skipped as well.  The loss is not part of the    */
+/* predicate: under data parallelism it is rank-local, while sumsq is taken  */
+/* after the all-reduce and is the same on every rank.                       */
+/* ok:      every byte written -- param, exp_avg, exp_avg_sq, the bf16 copy, */
+/*          tensor_steps, *step_dev -- is what the unguarded call writes.    */
+/* not ok:  every block of the update returns after reading the scalar; no   */
+/*          byte of param, exp_avg, exp_avg_sq, the bf16 copies or           */
+/*          tensor_steps is written.  *step_dev, the schedule position,      */
+/*          still advances by one.                                           */
+/* tensor_steps (the per-parameter bias-correction counts) and guard_dev are */
+/* required.  guard_dev points at one mdemi_guard_state in device memory     */
+/* that the trailing tick kernel updates; the host zero-initialises it with  */
+/* last_skipped = -1.  It lives at a fixed address, so a captured hipGraph   */
+/* advances it on every replay.                                              */
+/* ------------------------------------------------------------------------ */
+typedef struct mdemi_guard_state {
+  int32_t skipped;      /* steps dropped so far */
+  int32_t consecutive;  /* length of the current streak of dropped steps; 0 after an applied step */
+  int32_t last_skipped; /* 0-based index of the last dropped step: *step_dev before the call */
+                        /* (capturable form) or `calls` before the call (host form) */
+  int32_t calls;        /* guarded calls so far */
+} mdemi_guard_state;
+int mdemi_adamw_step_guarded16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                               const mdemi_adamw_group* groups_host, int32_t ngroups, const float* sumsq,
+                               float max_norm, float grad_scale, int32_t* tensor_steps, int64_t nitems,
+                               void* const* param16_dev, mdemi_guard_state* guard_dev, void* workspace,
+                               void* stream);
+int mdemi_adamw_step_dev_guarded16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                                   const mdemi_adamw_group* sched_dev, int32_t nsteps, int32_t ngroups,
+                                   int32_t* step_dev, int32_t* tensor_steps, const float* sumsq, float max_norm,
+                                   float grad_scale, int64_t nitems, void* const* param16_dev,
+                                   mdemi_guard_state* guard_dev, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "mdemi_ext.h"
 
 namespace mdemi {
 
@@ -225,12 +226,20 @@ __device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
   return coef < 1.f ? coef : 1.f;
 }
 
+// GUARD (mdemi_adamw_step_guarded16 / mdemi_adamw_step_dev_guarded16): a block whose
+// gradients are not finite -- !isfinite(sumsq[0]), the scalar mdemi_grad_sumsq left --
+// returns after that one read and writes nothing.  The unguarded instantiation compiles
+// to the body it had before the template.
+template <bool GUARD>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(const mdemi_tensor_ref* __restrict__ tl,
                                                             const int* __restrict__ chunk_tensor,
                                                             const int* __restrict__ chunk_index, AdamGroups groups,
                                                             const float* __restrict__ sumsq, float max_norm, float gs,
                                                             int step, const int* __restrict__ tensor_steps,
                                                             void* const* __restrict__ p16tab) {
+  if constexpr (GUARD) {
+    if (!isfinite(sumsq[0])) return;
+  }
   const int item = blockIdx.x;
   const int ti = chunk_tensor[item];
   const mdemi_tensor_ref t = tl[ti];
@@ -242,6 +251,7 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(const mdemi_tensor_r
 
 // capturable form: hyperparameters of step s (= *step_dev, steps already taken)
 // from row min(s, nsteps - 1) of a device schedule table
+template <bool GUARD>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_dev_kernel(const mdemi_tensor_ref* __restrict__ tl,
                                                                 const int* __restrict__ chunk_tensor,
                                                                 const int* __restrict__ chunk_index,
@@ -251,6 +261,9 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_dev_kernel(const mdemi_tens
                                                                 const int* __restrict__ tensor_steps,
                                                                 const float* __restrict__ sumsq, float max_norm,
                                                                 float gs, void* const* __restrict__ p16tab) {
+  if constexpr (GUARD) {
+    if (!isfinite(sumsq[0])) return;
+  }
   const int item = blockIdx.x;
   const int ti = chunk_tensor[item];
   const mdemi_tensor_ref t = tl[ti];
@@ -269,6 +282,32 @@ __global__ __launch_bounds__(256) void step_tick_kernel(int* step_dev, const mde
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (step_dev && i == 0) step_dev[0] += 1;
   if (tensor_steps && i < nt) tensor_steps[tl[i].step_slot] += 1;
+}
+
+// the guarded step's tick, on the same predicate as its update kernel: an applied step
+// advances the per-parameter counters and clears the streak; a skipped one leaves them and is
+// counted.  The schedule position *step_dev (capturable form) advances either way.  One thread
+// owns *step_dev and the guard state; every address is fixed, so a captured graph advances
+// them on every replay.
+__global__ __launch_bounds__(256) void guarded_tick_kernel(int* step_dev, const mdemi_tensor_ref* __restrict__ tl,
+                                                           int nt, int* tensor_steps,
+                                                           const float* __restrict__ sumsq,
+                                                           mdemi_guard_state* __restrict__ guard) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool ok = isfinite(sumsq[0]);
+  if (i == 0) {
+    const int at = step_dev ? step_dev[0] : guard->calls;  // 0-based index of this step
+    if (ok) {
+      guard->consecutive = 0;
+    } else {
+      guard->skipped += 1;
+      guard->consecutive += 1;
+      guard->last_skipped = at;
+    }
+    guard->calls += 1;
+    if (step_dev) step_dev[0] = at + 1;
+  }
+  if (ok && i < nt) tensor_steps[tl[i].step_slot] += 1;
 }
 
 }  // namespace mdemi
@@ -420,7 +459,7 @@ extern "C" int mdemi_adamw_step16(const mdemi_tensor_ref* tensors_dev, int32_t n
   const int* ct = (const int*)workspace;
   const int* ci = ct + nitems;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, g, sumsq,
+  hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, g, sumsq,
                      max_norm, grad_scale, step, (const int*)tensor_steps, param16_dev);
   if (tensor_steps)
     hipLaunchKernelGGL(step_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)nullptr,
@@ -447,12 +486,70 @@ extern "C" int mdemi_adamw_step_dev16(const mdemi_tensor_ref* tensors_dev, int32
   const int* ct = (const int*)workspace;
   const int* ci = ct + nitems;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, sched_dev,
+  hipLaunchKernelGGL(adamw_dev_kernel<false>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, sched_dev,
                      nsteps, ngroups, (const int*)step_dev, (const int*)tensor_steps, sumsq, max_norm, grad_scale,
                      param16_dev);
   hipLaunchKernelGGL(step_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)step_dev,
                      tensors_dev, ntensors, (int*)tensor_steps);
   return check_launch("adamw_step_dev");
+}
+
+// Guarded forms (train.nonfinite: "skip"): the same update when isfinite(sumsq[0]), no write
+// at all otherwise; see include/mdemi_ext.h.
+static int guarded_args(const char* what, const void* tensors_dev, int32_t ntensors, int32_t ngroups,
+                        const int32_t* tensor_steps, const float* sumsq, float grad_scale, int64_t nitems,
+                        const mdemi_guard_state* guard_dev, const void* workspace) {
+  if (!sumsq) {
+    set_error("%s: sumsq is required (mdemi_grad_sumsq over the same table): the skip predicate reads it", what);
+    return MDEMI_EINVAL;
+  }
+  MDEMI_REQUIRE(tensors_dev && ntensors > 0 && ngroups > 0 && ngroups <= 4 && tensor_steps && guard_dev &&
+                    nitems > 0 && nitems <= INT32_MAX && workspace && grad_scale > 0.f,
+                "%s: bad args (tensor_steps and guard_dev are required)", what);
+  return MDEMI_OK;
+}
+
+extern "C" int mdemi_adamw_step_guarded16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                                          const mdemi_adamw_group* groups_host, int32_t ngroups, const float* sumsq,
+                                          float max_norm, float grad_scale, int32_t* tensor_steps, int64_t nitems,
+                                          void* const* param16_dev, mdemi_guard_state* guard_dev, void* workspace,
+                                          void* stream) {
+  const int rc = guarded_args("adamw_step_guarded", tensors_dev, ntensors, ngroups, tensor_steps, sumsq, grad_scale,
+                              nitems, guard_dev, workspace);
+  if (rc != MDEMI_OK) return rc;
+  MDEMI_REQUIRE(groups_host, "adamw_step_guarded: bad args (groups_host)");
+  AdamGroups g;
+  for (int i = 0; i < ngroups; ++i) g.g[i] = groups_host[i];
+  for (int i = ngroups; i < 4; ++i) g.g[i] = groups_host[0];
+  const int* ct = (const int*)workspace;
+  const int* ci = ct + nitems;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, g,
+                     sumsq, max_norm, grad_scale, 0, (const int*)tensor_steps, param16_dev);
+  hipLaunchKernelGGL(guarded_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)nullptr,
+                     tensors_dev, ntensors, (int*)tensor_steps, sumsq, guard_dev);
+  return check_launch("adamw_step_guarded");
+}
+
+extern "C" int mdemi_adamw_step_dev_guarded16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                                              const mdemi_adamw_group* sched_dev, int32_t nsteps, int32_t ngroups,
+                                              int32_t* step_dev, int32_t* tensor_steps, const float* sumsq,
+                                              float max_norm, float grad_scale, int64_t nitems,
+                                              void* const* param16_dev, mdemi_guard_state* guard_dev,
+                                              void* workspace, void* stream) {
+  const int rc = guarded_args("adamw_step_dev_guarded", tensors_dev, ntensors, ngroups, tensor_steps, sumsq,
+                              grad_scale, nitems, guard_dev, workspace);
+  if (rc != MDEMI_OK) return rc;
+  MDEMI_REQUIRE(sched_dev && nsteps > 0 && step_dev, "adamw_step_dev_guarded: bad args (schedule)");
+  const int* ct = (const int*)workspace;
+  const int* ci = ct + nitems;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(adamw_dev_kernel<true>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci,
+                     sched_dev, nsteps, ngroups, (const int*)step_dev, (const int*)tensor_steps, sumsq, max_norm,
+                     grad_scale, param16_dev);
+  hipLaunchKernelGGL(guarded_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)step_dev,
+                     tensors_dev, ntensors, (int*)tensor_steps, sumsq, guard_dev);
+  return check_launch("adamw_step_dev_guarded");
 }
 
 // Stochastic depth (timm DropPath, swin_transformer.py:181,243-244):

@@ -109,6 +109,10 @@ class TelemetryState(ctypes.Structure):  # include/mdemi_ext.h mdemi_telemetry_s
     _fields_ = [("pushed", i32), ("nonfinite_steps", i32), ("first_nonfinite", i32), ("_pad", i32)]
 
 
+class GuardState(ctypes.Structure):  # include/mdemi_ext.h mdemi_guard_state
+    _fields_ = [("skipped", i32), ("consecutive", i32), ("last_skipped", i32), ("calls", i32)]
+
+
 AUG_MAX_SPANS = 8  # include/mdemi_ext.h MDEMI_AUG_MAX_SPANS
 
 
@@ -243,6 +247,10 @@ _SIGS = {
     "mdemi_pad_replicate": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "mdemi_param_sumsq": (ctypes.c_int, [vp, i32, i64, vp, vp, vp]),
     "mdemi_telemetry_push": (ctypes.c_int, [vp, i32, vp, vp, vp, vp]),
+    "mdemi_adamw_step_guarded16": (ctypes.c_int, [vp, i32, ctypes.POINTER(AdamWGroup), i32, vp, f32, f32, vp, i64, vp,
+                                                  vp, vp, vp]),
+    "mdemi_adamw_step_dev_guarded16": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, f32, f32, i64, vp, vp, vp,
+                                                      vp]),
 }
 
 _lib = None

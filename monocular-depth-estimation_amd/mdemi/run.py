@@ -34,6 +34,9 @@ def _args(argv):
     ap.add_argument("--precision", default=None, choices=["fp32", "fp32e", "bf16"])
     ap.add_argument("--drop-path", type=float, default=None, help="override the model's stochastic-depth rate")
     ap.add_argument("--seed", type=int, default=0, help="weight init, epoch permutations and augmentation draws")
+    ap.add_argument("--nonfinite", default=None, choices=["stop", "skip"],
+                    help="override the config's train.nonfinite: stop at a non-finite step (the default), or "
+                         "skip its update on the device and go on")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many optimizer steps (in all)")
     return ap.parse_args(argv)
 
@@ -84,6 +87,10 @@ def main(argv=None) -> int:
 
     # 1. the config
     opt = parse(args.opt, write_option=rank == 0 and not args.test)
+    if args.nonfinite is not None:
+        opt.setdefault("train", {})["nonfinite"] = args.nonfinite
+    from .train.builder import nonfinite_policy
+    nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
     out_dir = opt["output_dir"]
     data_type = opt["dataset"]["data_type"].upper()
     eval_opt = dict(opt.get("eval", {}))

@@ -25,6 +25,10 @@ unchanged, onto this framework's objects:
                         -> OneCycleLR (max_lr = each group's lr; total = epoch x
                            optimizer steps per epoch)
   train.grad_norm       -> global-norm clip folded into the AdamW step
+  train.nonfinite       -> "stop" (default): a non-finite step ends the run; "skip": the guarded
+                           AdamW step drops it on the device and the run goes on, until more
+                           than train.max_consecutive_skips (default 10) follow one another
+                           (a decision; the reference does not pin it)
   train.num_accum       -> micro-steps accumulated per optimizer step (DDP no_sync
                            on all but the last)
   train.freeze_encoder_bn / freeze_all_bn -> BatchNorm modules kept in eval mode
@@ -135,12 +139,28 @@ def param_groups(model, opt):
     return [{"params": list(model.parameters()), "lr": lr}]
 
 
+NONFINITE_POLICIES = ("stop", "skip")
+
+
+def nonfinite_policy(opt):
+    """(train.nonfinite, train.max_consecutive_skips), validated."""
+    tr = opt.get("train", {})
+    policy = tr.get("nonfinite", "stop")
+    if policy not in NONFINITE_POLICIES:
+        raise ValueError(f"train.nonfinite must be one of {NONFINITE_POLICIES}, got {policy!r}")
+    limit = tr.get("max_consecutive_skips", 10)
+    if isinstance(limit, bool) or not isinstance(limit, int) or limit < 0:
+        raise ValueError(f"train.max_consecutive_skips must be a non-negative integer, got {limit!r}")
+    return policy, limit
+
+
 def build_optimizer(model, opt, capturable=False):
     o = opt.get("optimizer", {})
     betas = tuple(float(b) for b in o.get("betas", (0.9, 0.999)))
+    kw = {"skip_nonfinite": True} if nonfinite_policy(opt)[0] == "skip" else {}
     return FusedAdamW(param_groups(model, opt), lr=float(o["lr"]), betas=betas, eps=float(o.get("eps", 1e-8)),
                       weight_decay=float(o.get("weight_decay", 0.0)),
-                      max_grad_norm=float(opt.get("train", {}).get("grad_norm", 0.0)), capturable=capturable)
+                      max_grad_norm=float(opt.get("train", {}).get("grad_norm", 0.0)), capturable=capturable, **kw)
 
 
 def optimizer_steps_per_epoch(opt, world=1, images=None):
@@ -347,6 +367,14 @@ class Trainer:
         from ..utils.common_utils import save_checkpoint
         save_checkpoint(prefix, self.model, self.optimizer, self.epoch, current_iter, best_value, save_dir,
                         best_epoch=best_epoch, best_iter=best_iter, model_only=model_only)
+
+    def buffers_finite(self):
+        """Whether every floating-point buffer of the model (BatchNorm running statistics) is
+        finite: one torch.isfinite per buffer and one host read.  The guarded optimizer step
+        cannot protect them -- a forward that overflowed has already written its batch
+        statistics -- so the driver asks before a checkpoint under train.nonfinite "skip"."""
+        bad = [~torch.isfinite(b).all() for b in self.model.buffers() if torch.is_floating_point(b)]
+        return not bad or not bool(torch.stack(bad).any().item())
 
     def resume(self, path):
         """Load a save_checkpoint file (the reference's format): model weights, optimizer

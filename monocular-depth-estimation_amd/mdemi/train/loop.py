@@ -14,6 +14,12 @@ parity and what is a decision is listed in DESIGN.md §1c.  In short:
                 (seed, epoch, step, micro, rank), so the data of any step is a pure function of
                 where the step is -- a resumed run continues the identical stream
   fit           the loop; one host synchronisation per print_freq steps (Telemetry.drain)
+
+train.nonfinite "skip": the guarded optimizer step has already dropped a step whose gradient
+sum of squares was not finite (the record's MDEMI_STEP_GRAD_NONFINITE flag is that same
+predicate), so fit counts such records instead of stopping.  A skipped step is still a step:
+the schedule, the epoch stream and step_rng are functions of the step index and advance;
+only the weights, the moments and the bias-correction counts stand still.
 """
 from __future__ import annotations
 
@@ -25,8 +31,9 @@ import time
 
 import torch
 
+from .. import _lib as L
 from ..utils.dist_utils import all_reduce_dict
-from .builder import optimizer_steps_per_epoch
+from .builder import nonfinite_policy, optimizer_steps_per_epoch
 from .telemetry import NonFiniteStep
 
 LOG_NAME = "log.jsonl"
@@ -111,6 +118,14 @@ def _finite_mean(vals):
     return sum(vals) / len(vals) if vals else None
 
 
+class _Stop(Exception):
+    """fit's skip mode gives up: ``rec`` goes to log.jsonl, ``msg`` to the log."""
+
+    def __init__(self, rec, msg):
+        super().__init__(msg)
+        self.rec, self.msg = rec, msg
+
+
 def _append(path, rec):
     with open(path, "a", encoding="utf-8") as f:
         f.write(json.dumps(rec) + "\n")
@@ -119,6 +134,15 @@ def _append(path, rec):
 def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps_per_epoch=None, start_epoch=0,
         start_step=0, max_steps=None, rank=0, world=1, best=None, log=print):
     """Run the train loop; returns the process exit code (0, or 1 after a non-finite step).
+
+    train.nonfinite "skip" (the trainer's optimizer is FusedAdamW(skip_nonfinite=True)): a
+    record flagged GRAD_NONFINITE is a step the device dropped -- logged as {"type":
+    "skipped", step, epoch, iter}, counted in the train record's "skipped" (window) and
+    "skipped_total" and kept out of its means; one flagged LOSS_NONFINITE only was applied
+    with a finite gradient and is logged as {"type": "nonfinite_loss", ...}.  The run ends
+    with exit code 1 when more than train.max_consecutive_skips steps in a row were skipped,
+    or when a checkpoint is due and the parameter norm or a floating-point buffer of the
+    model is not finite (nothing is written then, as under "stop").
 
     train_batches yields one list of train.num_accum (image, gt) micro-batches per optimizer
     step, starting at (start_epoch, start_step); validate() returns the metric dict
@@ -144,23 +168,99 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
         os.makedirs(out_dir, exist_ok=True)
     best_value, best_epoch, best_iter = best if best is not None else (math.inf, None, None)
 
+    policy, max_skips = nonfinite_policy(opt)
+    skip_mode = policy == "skip"
+    guard = getattr(trainer.optimizer, "skipped_steps", None) if skip_mode else None
+    if skip_mode and (guard is None or not getattr(trainer.optimizer, "skip_nonfinite", True)):
+        # without the guarded update a flagged step HAS written its NaNs: never count it as skipped
+        raise ValueError('fit: train.nonfinite "skip" needs an optimizer with the guarded step '
+                         "(FusedAdamW(skip_nonfinite=True); build_from_config passes it)")
+
     done = start_epoch * spe + start_step  # optimizer steps completed (the global step)
     base = done  # telemetry record i is global step base + i + 1
     window, dropped = [], 0
+    # skip mode: steps skipped in the window / in this call, the current streak of skipped
+    # steps and the global step it began at, and the optimizer's counters when fit began
+    w_skipped = skipped_total = 0
+    skipped0, streak = guard() if guard is not None else (0, 0)
+    streak_first = base - streak + 1
     t_window, n_window = time.perf_counter(), 0
     validated_at = None
     lr_used = None
 
+    def where(gstep):
+        e, s = divmod(gstep - 1, spe)
+        return {"step": gstep, "epoch": e, "iter": s + 1}
+
     def drain():
-        nonlocal dropped
-        d = telemetry.drain()
-        window.extend(d.records)
+        nonlocal dropped, w_skipped, skipped_total, streak, streak_first
+        if not skip_mode:
+            d = telemetry.drain()
+            window.extend(d.records)
+            dropped += d.dropped
+            return
+        d = telemetry.drain(raise_on_nonfinite=False)
         dropped += d.dropped
+        lines, over = [], None  # over: (first step, length) of a streak beyond the limit
+        for r in d.records:
+            gstep = base + r.index + 1
+            if r.flags & L.STEP_GRAD_NONFINITE:
+                w_skipped += 1
+                skipped_total += 1
+                streak += 1
+                if streak == 1:
+                    streak_first = gstep
+                if streak > max_skips:
+                    over = (streak_first, streak)
+                lines.append({"type": "skipped", **where(gstep)})
+                continue
+            streak = 0
+            if r.flags & L.STEP_LOSS_NONFINITE:
+                lines.append({"type": "nonfinite_loss", **where(gstep)})
+            window.append(r)
+        if guard is not None:
+            # the optimizer's own counters (mdemi_guard_state), read at the same point: they
+            # must tell the same story as the records; when the ring overflowed they stand in
+            dev_skipped, dev_streak = guard()
+            if d.dropped:
+                skipped_total, streak = dev_skipped - skipped0, dev_streak
+                streak_first = done - streak + 1
+                if streak > max_skips:
+                    over = (streak_first, streak)
+            elif (dev_skipped - skipped0, dev_streak) != (skipped_total, streak):
+                raise RuntimeError(f"fit: the telemetry records count {skipped_total} skipped step(s), streak "
+                                   f"{streak}; the optimizer's guard state says {dev_skipped - skipped0}, streak "
+                                   f"{dev_streak}")
+        if rank == 0:
+            for rec in lines:
+                _append(log_path, rec)
+                log(json.dumps(rec))
+        if over is not None:
+            first, n = over
+            raise _Stop({"type": "skip_limit", **where(first), "consecutive": n},
+                        f"{n} consecutive optimizer steps skipped for non-finite gradients, the first at step "
+                        f"{first} (epoch {where(first)['epoch']}, iter {where(first)['iter']}); "
+                        f"train.max_consecutive_skips is {max_skips}: no checkpoint written, stopping.")
+
+    def require_finite_model():
+        """Skip mode, before a checkpoint: the rule 'never checkpoint a non-finite model' for
+        what the guarded step cannot cover (BatchNorm running statistics written by a forward
+        that overflowed).  Buffers are rank-local, so the verdict is reduced over the ranks."""
+        pn = trainer.optimizer.param_norm()
+        bad_norm = not math.isfinite(float(pn.item() if hasattr(pn, "item") else pn))
+        ok_buffers = getattr(trainer, "buffers_finite", None)
+        bad_buf = ok_buffers is not None and not ok_buffers()
+        red = all_reduce_dict({"norm": float(bad_norm), "buffers": float(bad_buf)}, op="mean")
+        if red["norm"] > 0 or red["buffers"] > 0:
+            what = "parameter norm" if red["norm"] > 0 else "model buffer (BatchNorm running statistics)"
+            raise _Stop({"type": "nonfinite", **where(done), "count": 0, "what": what},
+                        f"non-finite {what} at optimizer step {done} with a checkpoint due: no checkpoint written, "
+                        "stopping.")
 
     def emit_train(epoch, it):
-        nonlocal window, dropped, t_window, n_window
+        nonlocal window, dropped, t_window, n_window, w_skipped
         now = time.perf_counter()
-        losses = [r.loss for r in window]
+        losses = [r.loss for r in window if not r.flags & L.STEP_LOSS_NONFINITE]
         norms = [math.sqrt(r.grad_sumsq) for r in window if r.grad_sumsq >= 0]
         rate = n_window * batch * num_accum / max(now - t_window, 1e-9)
         red = all_reduce_dict({"loss": float(_finite_mean(losses) or 0.0), "images_per_sec": float(rate)}, op="mean")
@@ -170,6 +270,9 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
                "param_norm": float(pn.item() if hasattr(pn, "item") else pn),
                "lr": lr_used,
                "images_per_sec": red["images_per_sec"] * world, "dropped": dropped}
+        if skip_mode:
+            rec.update(skipped=w_skipped, skipped_total=skipped_total)
+            w_skipped = 0
         if rank == 0:
             _append(log_path, rec)
             log(json.dumps(rec))
@@ -178,6 +281,8 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     def run_validation(epoch, it):
         nonlocal best_value, best_epoch, best_iter, validated_at, t_window
         t0 = time.perf_counter()
+        if skip_mode:
+            require_finite_model()
         metrics = {k: float(v) for k, v in validate().items()}
         if hasattr(trainer, "train_mode"):
             trainer.train_mode()  # evaluate() restores model.train(); frozen BatchNorms go back to eval
@@ -220,6 +325,8 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
         if done > base and validated_at != done and done < total:
             # ended early (max_steps): leave a resumable latest.pth, without a validation
             drain()
+            if skip_mode:
+                require_finite_model()
             if rank == 0:
                 epoch, step = divmod(done - 1, spe)
                 trainer.epoch = epoch
@@ -233,5 +340,10 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
         if rank == 0:
             _append(log_path, {"type": "nonfinite", "step": bad, "epoch": epoch, "iter": step + 1, "count": e.count})
         log(msg)
+        return 1
+    except _Stop as e:
+        if rank == 0:
+            _append(log_path, e.rec)
+        log(e.msg)
         return 1
     return 0

@@ -26,10 +26,19 @@ class FusedAdamW:
     from a schedule table (set_schedule; default: the groups' current values) indexed by
     a device step counter, so the whole step can live in a captured hipGraph
     (mdemi_adamw_step_dev).  The host mirrors (step_count, steps) are advanced by the
-    caller after each replay (``replayed()``; Trainer does)."""
+    caller after each replay (``replayed()``; Trainer does).
+
+    skip_nonfinite=True (train.nonfinite: "skip"): every step computes the gradient sum of
+    squares, also with the clip off, and goes through the guarded entry points
+    (mdemi_adamw_step_guarded16 / mdemi_adamw_step_dev_guarded16): a step whose sum is not
+    finite writes no weight, moment, bf16 copy or per-parameter count -- decided on the device,
+    no host synchronisation.  ``step_count`` stays the schedule position and advances on every
+    step; the per-parameter counts do not advance on a skipped one, so the ``steps`` mirror is
+    read back from the device where it is needed (state_dict, skipped_steps) instead of being
+    advanced blindly."""
 
     def __init__(self, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0,
-                 capturable=False):
+                 capturable=False, skip_nonfinite=False):
         if isinstance(param_groups, torch.Tensor) or (isinstance(param_groups, (list, tuple)) and param_groups and
                                                       isinstance(param_groups[0], torch.Tensor)):
             param_groups = [{"params": list(param_groups)}]
@@ -63,6 +72,8 @@ class FusedAdamW:
         self._sumsq = None
         self._psumsq = None  # param_norm()'s sum of squares
         self.capturable = bool(capturable)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._guard_dev = None  # mdemi_guard_state (skipped, consecutive, last_skipped, calls)
         self._sched_rows = None  # host schedule [(lr, beta1, beta2, eps, wd) per group] per step
         self._sched_dev = None
         self._step_dev = None
@@ -196,24 +207,37 @@ class FusedAdamW:
             if capturing:
                 raise RuntimeError("FusedAdamW: step counters must exist before hipGraph capture")
             self._steps_dev = torch.tensor(self.steps, dtype=torch.int32).to(dev)
+        if self.skip_nonfinite and self._guard_dev is None:
+            if capturing:
+                raise RuntimeError("FusedAdamW: the guard state must exist before hipGraph capture")
+            self._guard_dev = torch.tensor([0, 0, -1, 0], dtype=torch.int32).to(dev)
         if self._sumsq is None:
             self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
         gs = float(self.grad_scale)
-        if self.max_grad_norm > 0:
+        if self.max_grad_norm > 0 or self.skip_nonfinite:
             L.check(lib.mdemi_grad_sumsq(tl_ptr, nt, ni, gs, self._sumsq.data_ptr(), ws_ptr, L.stream()), "grad_sumsq")
         clip = self._sumsq.data_ptr() if self.max_grad_norm > 0 else None
         steps_ptr = self._steps_dev.data_ptr()
-        if self.capturable:
+        if self.skip_nonfinite:
+            sumsq, guard = self._sumsq.data_ptr(), self._guard_dev.data_ptr()
+            if self.capturable:
+                sched, nsteps = self._device_schedule(dev, self.step_count)
+                L.check(lib.mdemi_adamw_step_dev_guarded16(tl_ptr, nt, sched.data_ptr(), nsteps, len(self.param_groups),
+                                                           self._step_dev.data_ptr(), steps_ptr, sumsq,
+                                                           self.max_grad_norm, gs, ni, p16_ptr, guard, ws_ptr,
+                                                           L.stream()), "adamw_step_dev_guarded")
+            else:
+                L.check(lib.mdemi_adamw_step_guarded16(tl_ptr, nt, self._host_groups(), len(self.param_groups), sumsq,
+                                                       self.max_grad_norm, gs, steps_ptr, ni, p16_ptr, guard, ws_ptr,
+                                                       L.stream()), "adamw_step_guarded")
+        elif self.capturable:
             sched, nsteps = self._device_schedule(dev, self.step_count)
             L.check(lib.mdemi_adamw_step_dev16(tl_ptr, nt, sched.data_ptr(), nsteps, len(self.param_groups),
                                                self._step_dev.data_ptr(), steps_ptr, clip, self.max_grad_norm, gs,
                                                ni, p16_ptr, ws_ptr, L.stream()), "adamw_step_dev")
         else:
-            groups = (L.AdamWGroup * len(self.param_groups))()
-            for i, g in enumerate(self.param_groups):
-                groups[i].lr, (groups[i].beta1, groups[i].beta2) = g["lr"], g["betas"]
-                groups[i].eps, groups[i].weight_decay = g["eps"], g["weight_decay"]
-            L.check(lib.mdemi_adamw_step16(tl_ptr, nt, groups, len(self.param_groups), clip, self.max_grad_norm, gs,
+            L.check(lib.mdemi_adamw_step16(tl_ptr, nt, self._host_groups(), len(self.param_groups), clip,
+                                           self.max_grad_norm, gs,
                                            self.step_count + 1, steps_ptr, ni, p16_ptr, ws_ptr, L.stream()),
                     "adamw_step")
         for p, b16 in self._b16.items():  # the update wrote these copies at the new weight epoch
@@ -221,6 +245,13 @@ class FusedAdamW:
                 _mf.set_b16(p, b16)
         if not capturing:  # a capture records the step; replays advance the mirrors (replayed())
             self.replayed()
+
+    def _host_groups(self):
+        groups = (L.AdamWGroup * len(self.param_groups))()
+        for i, g in enumerate(self.param_groups):
+            groups[i].lr, (groups[i].beta1, groups[i].beta2) = g["lr"], g["betas"]
+            groups[i].eps, groups[i].weight_decay = g["eps"], g["weight_decay"]
+        return groups
 
     # ---- step telemetry (train.loop) ----
     def _table(self, what):
@@ -235,7 +266,7 @@ class FusedAdamW:
         mdemi_grad_sumsq over the step's table.  Either way the tensor is the one persistent
         ``_sumsq`` buffer: its address never changes, so the call can sit in a captured step."""
         _, _, tl_ptr, ws_ptr, nt, ni, _ = self._table("grad_sumsq_tensor")
-        if not self.max_grad_norm > 0:
+        if not (self.max_grad_norm > 0 or self.skip_nonfinite):
             L.check(L.load().mdemi_grad_sumsq(tl_ptr, nt, ni, float(self.grad_scale), self._sumsq.data_ptr(), ws_ptr,
                                               L.stream()), "grad_sumsq")
         return self._sumsq
@@ -253,16 +284,38 @@ class FusedAdamW:
         return torch.sqrt(self._psumsq[0])
 
     def replayed(self):
-        """Advance the host mirrors by one executed step over the current table's parameters."""
+        """Advance the host mirrors by one executed step over the current table's parameters.
+        Under skip_nonfinite only the schedule position advances here: whether the
+        per-parameter counts moved was decided on the device (_refresh_steps)."""
         self.step_count += 1
+        if self.skip_nonfinite:
+            return
         for s in self._tbl_slots:
             self.steps[s] += 1
+
+    def _refresh_steps(self):
+        """skip_nonfinite: read the per-parameter counts back from the device (one small copy)."""
+        if self.skip_nonfinite and self._steps_dev is not None:
+            self.steps = [int(v) for v in self._steps_dev.tolist()]
+
+    def skipped_steps(self):
+        """(skipped, consecutive): steps the guarded update has dropped so far and the length of
+        the current streak, with one small device-to-host copy (a synchronisation: call it
+        where the telemetry ring is drained, not per step).  Also refreshes ``steps``."""
+        if not self.skip_nonfinite:
+            raise RuntimeError("FusedAdamW.skipped_steps: built without skip_nonfinite")
+        if self._guard_dev is None:
+            return 0, 0
+        self._refresh_steps()
+        g = self._guard_dev.tolist()
+        return int(g[0]), int(g[1])
 
     def state_dict(self):
         """torch.optim.AdamW's layout: state keyed by each parameter's position across
         param_groups (not by the order gradients first appeared), a per-parameter "step",
         and "params" index lists per group -- so save_checkpoint files
         (common_utils.py:12-31 optimizer_state_dict) round-trip with torch's AdamW."""
+        self._refresh_steps()
         state, groups, idx = {}, [], 0
         for g in self.param_groups:
             ids = []
@@ -277,7 +330,13 @@ class FusedAdamW:
             gd.update(amsgrad=False, maximize=False, foreach=None, capturable=self.capturable,
                       differentiable=False, fused=None, params=ids)
             groups.append(gd)
-        return {"state": state, "param_groups": groups}
+        sd = {"state": state, "param_groups": groups}
+        if self.skip_nonfinite:
+            # the schedule position: with skipped steps it runs ahead of every per-parameter
+            # count, so max(steps) no longer recovers it.  torch.optim's loader ignores unknown
+            # top-level keys: the file still loads into torch.optim.AdamW
+            sd["schedule_step"] = int(self.step_count)
+        return sd
 
     def load_state_dict(self, sd):
         """Load torch.optim.AdamW's layout (or our own state_dict).  Existing state tensors
@@ -314,7 +373,7 @@ class FusedAdamW:
             self.layout_version += 1
         self.state = new_state
         self.steps = steps
-        self.step_count = max(steps) if steps else 0
+        self.step_count = schedule_position(sd, steps)
         if self._steps_dev is not None:
             self._steps_dev.copy_(torch.tensor(steps, dtype=torch.int32))
         if self._step_dev is not None:
@@ -326,6 +385,19 @@ class FusedAdamW:
             rows = [[(g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"]) for g in self.param_groups]]
             flat = [v for r in rows for e in r for v in (*e, 0.0)]
             self._sched_dev[0].copy_(torch.tensor(flat, dtype=torch.float32))
+
+
+def schedule_position(sd, steps):
+    """Optimizer steps a loaded state has behind it: its top-level "schedule_step" when it
+    carries one (FusedAdamW(skip_nonfinite=True).state_dict(): skipped steps advance the
+    schedule and no per-parameter count), else the largest per-parameter count."""
+    if sd.get("schedule_step") is not None:
+        s = int(sd["schedule_step"])
+        if s < (max(steps) if steps else 0):
+            raise ValueError(f"loaded state dict: schedule_step {s} is behind a per-parameter step "
+                             f"{max(steps)}")
+        return s
+    return max(steps) if steps else 0
 
 
 class OneCycleLR:

@@ -2,9 +2,11 @@
 ``mdemi_telemetry_push`` (csrc/telemetry.hip) appends once per optimizer step, on the
 step's own stream -- inside the captured hipGraph in graph mode -- and that the host
 reads with one copy every ``train.print_freq`` steps (train.loop.fit).  Nothing here
-synchronises per step.  The push also flags a non-finite loss or gradient norm; the
-AdamW kernels are unchanged, so a flagged step has already poisoned the weights and the
-driver stops instead of checkpointing them."""
+synchronises per step.  The push also flags a non-finite loss or gradient norm.  Under the
+default policy (train.nonfinite: "stop") the unguarded AdamW kernels have already written
+such a step into the weights and the driver stops instead of checkpointing them; under
+"skip" the guarded update dropped it on the same scalar and the same predicate, so a record
+flagged MDEMI_STEP_GRAD_NONFINITE is a skipped step."""
 from __future__ import annotations
 
 import ctypes
@@ -98,12 +100,14 @@ class Telemetry:
         state = {"pushed": int(st[0]), "nonfinite_steps": int(st[1]), "first_nonfinite": int(st[2])}
         return state, raw[_STATE_BYTES:].view(_REC_DTYPE)
 
-    def drain(self):
+    def drain(self, raise_on_nonfinite=True):
         """Drained(records, dropped, pushed): the StepRecords pushed since the last drain, in
         order; ``dropped`` counts those overwritten because more than ``capacity`` arrived in
-        between.  Raises NonFiniteStep when any recorded step was flagged."""
+        between.  Raises NonFiniteStep when any recorded step was flagged;
+        raise_on_nonfinite=False returns the flagged records with the others instead (their
+        ``flags`` say which), for a caller that handles them."""
         state, ring = self.snapshot()
-        if state["nonfinite_steps"] > 0:
+        if raise_on_nonfinite and state["nonfinite_steps"] > 0:
             raise NonFiniteStep(state["first_nonfinite"], state["nonfinite_steps"])
         recs, dropped = decode_ring(ring, state["pushed"], self._last_seen, self.capacity)
         self._last_seen = state["pushed"]

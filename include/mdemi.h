@@ -167,14 +167,16 @@ int mdemi_gemm_bf16x_supported(const mdemi_gemm_desc* d, const void* a16, const 
 /* tuning hook of the bf16-operand family: 0 = 128-row tile, 1 = 256-row tile, 2 = 128-row tile
  * with two K tiles per LDS stage, -1 = per-shape autotune (default; all bit-identical). */
 int mdemi_gemm_set_variant_b16(int32_t variant);
-/* tuning hook: pipelining variant (0..5, see gemm_f32.hip; -1 = time the
- * candidates once per distinct shape and cache the winner, the default -- all
- * variants produce bit-identical results) and tile raster (group_m > 0:
- * XCD-aware grouped raster, 0: plain).  Process-global. */
+/* tuning hook: variant of the fp32 family (0..12, F32_VARIANTS in csrc/gemm_plan.h;
+ * -1 = time the candidates once per distinct shape and cache the winner, the
+ * default -- all variants produce bit-identical results) and tile raster
+ * (group_m > 0: XCD-aware grouped raster, 0: plain).  Process-global. */
 int mdemi_gemm_set_variant(int32_t variant, int32_t group_m);
-/* tuning hook of the 16-bit family (mdemi_gemm_bf16 / mdemi_gemm_f32e): 0 = 128-row
- * tile with two LDS buffers, 1 = one buffer, 2 = 256-row tile; -1 = per-shape
- * autotune (default; all bit-identical). */
+/* tuning hook of the 16-bit family (mdemi_gemm_bf16 / mdemi_gemm_f32e), variants 0..4
+ * (M16_VARIANTS in csrc/gemm_plan.h): 0 = 128-row tile with two LDS buffers, 1 = one
+ * buffer, 2 = 256-row tile, 3 / 4 = bf16 LDS images on a 128- / 256-row tile (bf16
+ * only: mdemi_gemm_f32e runs variant 0 instead); -1 = per-shape autotune (default;
+ * all bit-identical). */
 int mdemi_gemm_set_variant_m16(int32_t variant);
 /* scheduling switches of the fp32 family (process-global; defaults from the environment:
  * MDEMI_GEMM_TAIL_SPLIT, on unless 0; MDEMI_GEMM_INLINE_REDUCE, off unless 1): tail_split --

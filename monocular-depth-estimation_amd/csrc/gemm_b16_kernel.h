@@ -232,7 +232,7 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wid >> 1, wn = wid & 1;
-  const GemmJob job = job_of(p);
+  const GemmJob job = job_of(p, blockIdx.x);
   const int b = job.b, sidx = job.sidx, tm = job.tm, tn = job.tn;
   const int bm = tm * BMT, bn = tn * GBN;
 
@@ -351,10 +351,12 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
 // profiles/round6/b16_variants_*.txt)
 template <int AL, int BL>
 static void (*pick_b16(int v))(GemmParams) {
+  constexpr const GemmVariant* T = B16_VARIANTS;  // tile rows: the host's table (gemm_plan.h)
+  static_assert(tiles_fixed(B16_VARIANTS, false, GBN, B16_BK), "this kernel's tiles are GBN x B16_BK");
   switch (v) {
-    case 0: return gemm_b16_kernel<AL, BL, 128, 3>;
-    case 1: return gemm_b16_kernel<AL, BL, 256, 2>;
-    case 2: return gemm_b16_kernel<AL, BL, 128, 2, 2>;
+    case 0: return gemm_b16_kernel<AL, BL, T[0].rows, 3>;
+    case 1: return gemm_b16_kernel<AL, BL, T[1].rows, 2>;
+    case 2: return gemm_b16_kernel<AL, BL, T[2].rows, 2, 2>;
     default: return nullptr;
   }
 }

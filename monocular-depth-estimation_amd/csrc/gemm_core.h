@@ -1,12 +1,13 @@
 // Shared pieces of the GEMM kernel families (gemm_f32.hip: exact-fp32 MFMA;
 // gemm_mfma16.hip: 16-bit-operand MFMA for the bf16 and split-fp32 modes):
 // parameters, branch-free buffer loads, the operand loaders (dense
-// k-contiguous, dense m/n-contiguous, implicit-im2col NHWC), the fused
-// epilogue value and the XCD-aware tile raster.
+// k-contiguous, dense m/n-contiguous, implicit-im2col NHWC) and the fused
+// epilogue value.  Variant tables, launch plan and tile raster: gemm_plan.h.
 #pragma once
 #include <utility>
 
 #include "common.h"
+#include "gemm_plan.h"
 
 namespace mdemi {
 
@@ -57,10 +58,7 @@ struct GemmParams {
   int binner;  // > 1: two-level batch (mdemi_gemm_desc.batch_inner)
   int64_t a_bs2, b_bs2, c_bs2;
   const float* rowscale; FastDiv fd_rs;  // optional per-row-group scale before the residual add
-  // Tail split (batch 1): row tiles [0, tiles_m1) take the whole K; the tiles_m row tiles
-  // below m_split = tiles_m1 * BMT are split `split` ways (the last, partial round of
-  // tiles), as is every tile of an ordinary split-K GEMM (tiles_m1 = 0).
-  int tiles_m1, m_split;
+  int tiles_m1, m_split;  // tail split: see GemmPlan (gemm_plan.h)
   int* tile_cnt;  // non-null: the last-arriving split of a tile combines the slabs (no reduce launch)
   float* rowsum_out;  // with tile_cnt and split row-sum partials: the last arriver writes the sums here
   void* c16;  // optional bf16 copy (RNE) of the final output, C's layout: the bf16 operand of a later GEMM
@@ -347,73 +345,6 @@ __device__ __forceinline__ float epilogue_value(const GemmParams& p, int b, int 
   if (p.res) v += p.res[(int64_t)b * p.res_bs + (int64_t)i * p.ldres + j];
   return v;
 }
-
-// tile (tm, tn) for a linear workgroup id over tiles_m x tiles_n tiles: XCD-aware
-// remap (blocks b, b+8, ... share an XCD), then grouped raster so concurrently running
-// tiles of one XCD reuse A row-panels (group_m rows of tiles) and B column-panels.
-// XCD-aware linear order: workgroup ids b, b+8, ... (one XCD) take one contiguous range
-// of [0, n), so neighbouring jobs share that XCD's L2.
-__device__ __forceinline__ int xcd_lin(int bid, int n) {
-  const int q = n / 8, r = n % 8;
-  const int xcd = bid % 8, idx = bid / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-__device__ __forceinline__ void tile_of(const GemmParams& p, int bid, int ntiles, int tiles_m, int& tm, int& tn,
-                                        bool remap = true) {
-  if (p.group_m <= 0) {  // plain raster: n fastest
-    tm = bid / p.tiles_n;
-    tn = bid % p.tiles_n;
-    return;
-  }
-  const int lin = remap ? xcd_lin(bid, ntiles) : bid;
-  const int per_group = p.group_m * p.tiles_n;
-  const int grp = lin / per_group;
-  const int first_m = grp * p.group_m;
-  const int gm = min(tiles_m - first_m, p.group_m);
-  const int in_grp = lin % per_group;
-  tm = first_m + in_grp % gm;
-  tn = in_grp / gm;
-}
-
-// What one workgroup computes: the whole-K tiles of the leading region come first in
-// launch order, then the split region's pieces (all tiles' piece 0, then piece 1, ...).
-struct GemmJob {
-  int b, sidx, tm, tn, cid;  // cid: counter slot of a split tile
-  bool split;
-};
-__device__ __forceinline__ GemmJob job_of(const GemmParams& p) {
-  GemmJob j;
-  const int n1 = p.tiles_m1 * p.tiles_n;
-  int bid = blockIdx.x;
-  if (bid < n1) {
-    j.b = 0; j.sidx = 0; j.split = false; j.cid = 0;
-    tile_of(p, bid, n1, p.tiles_m1, j.tm, j.tn);
-    return j;
-  }
-  bid -= n1;
-  const int n2 = p.tiles_m * p.tiles_n;
-  // The XCD remap runs over all (batch entry, K piece, tile) jobs, piece-major: every tile
-  // of one K piece (and of one batch entry) lands on one XCD, so a piece's operand rows --
-  // e.g. the NHWC pixels the im2col columns of a weight-gradient GEMM gather once per
-  // tap -- are fetched into one L2 instead of up to eight.
-  if (p.group_m > 0) bid = xcd_lin(bid, n2 * p.batch * p.split);
-  const int zb = bid / n2, t2 = bid - zb * n2;
-  j.b = zb / p.split;
-  j.sidx = zb - j.b * p.split;
-  j.split = p.split > 1;
-  int tm2;
-  tile_of(p, t2, n2, p.tiles_m, tm2, j.tn, false);
-  j.tm = p.tiles_m1 + tm2;
-  j.cid = j.b * n2 + tm2 * p.tiles_n + j.tn;
-  return j;
-}
-
-// precision modes of the GEMM entry points
-constexpr int GEMM_F32 = 0;   // exact-product fp32 MFMA (gemm_f32.hip)
-constexpr int GEMM_BF16 = 1;  // bf16 operands, fp32 accumulate (gemm_mfma16.hip, NP = 1)
-constexpr int GEMM_F32E = 2;  // fp32 as three bf16 planes, six products (gemm_mfma16.hip, NP = 3)
-constexpr int GEMM_B16 = 3;   // bf16 operands in HBM, direct-to-LDS (gemm_b16_kernel.h); numerics of GEMM_BF16
 
 void (*pick_kernel_m16(int al, int bl, int aop, int bop, int np, int v))(GemmParams);
 void (*pick_kernel_b16(int al, int bl, int v))(GemmParams);

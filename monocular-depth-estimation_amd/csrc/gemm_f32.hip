@@ -24,7 +24,7 @@
 // pitch 130).  Register-staged prefetch of the next K tile (issue early, write
 // late) into the second of two LDS buffers, one barrier per tile.  Block ids
 // are remapped so that the tiles an XCD runs concurrently share A row-panels
-// and B column-panels in that XCD's L2 (guide T1).  Variants: see pick_variant.
+// and B column-panels in that XCD's L2 (guide T1).  Variants: F32_VARIANTS (gemm_plan.h).
 #include "common.h"
 #include "gemm_core.h"
 #include "gemm_f32_kernel.h"
@@ -37,7 +37,6 @@
 
 namespace mdemi {
 
-// Deterministic split-K combine + epilogue: sums slabs in split order.
 // Deterministic split-K combine + epilogue: sums slabs in split order, four
 // consecutive columns per thread when N % 4 == 0; also folds the row-sum
 // partials [split][M] of a weight-gradient GEMM (bias gradient) in the same launch.
@@ -86,28 +85,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(GemmParams p, const fl
     }
 }
 
-
-// Variants (tools/gemm_bench.py on the NewCRFs-L07 480x640 bs=8 shapes,
-// profiles/r01_gemm_variants_v2.log):
-//   0: BK16, 2 LDS buffers, register prefetch, k-contiguous operands transposed
-//      into [k][row] images (ds_read_b32 fragments)
-//   1: as 0 with [row][k] images (ds_read_b128 fragments)
-//   2: as 0 capped at 128 VGPRs (4 waves/SIMD; spills)
-//   3: BK32, 2 buffers (2 workgroups/CU by LDS)   4: BK32, 1 buffer   5: as 3, [row][k]
-//   6: 256-row tile (waves of 128x64), BK32, 1 buffer   7: 256-row tile, BK16, 2 buffers
-//   (a BK64 single-buffer variant measured no faster than 4 on the model's shapes:
-//   profiles/round3/gemm_study_bk64.txt)
-//   8..12: direct-to-LDS staging (buffer_load ... lds, gemm_glds_kernel.h), dense 16-B
-//   operands without a load-time op only: 8 128-row BK32, 9 256-row BK16, 10 256-row
-//   BK32 (96 KiB, one workgroup per CU), 11 128-row BK16, 12 128-row x 192-column BK32 (the
-//   N = 192 / 576 shapes of the Swin stage 0: no half-empty 128-column tile)
-// No variant wins every shape (e.g. weight-gradient GEMMs over few output
-// tiles want BK32/2 buffers, token-major forwards want BK32/1 buffer), so by
-// default each distinct (layouts, ops, M, N, K, batch, split) is timed once
-// over the candidates on first use and the winner cached.  All variants add
-// the k products in the same order and split K at the same 32-element
-// boundaries, so the choice never changes a result bit.
-constexpr int NVARIANTS = 13;
 static int g_variant = -1;  // -1: autotune per shape
 // A/B switches (environment, read once): MDEMI_GEMM_TAIL_SPLIT=0 disables the tail split;
 // MDEMI_GEMM_INLINE_REDUCE=1 (fp32) / MDEMI_GEMM_INLINE_REDUCE_B16=1 (bf16) combine split-K
@@ -125,12 +102,11 @@ static bool env_set(const char* name) {
   const char* v = getenv(name);
   return v && v[0] && v[0] != '0';
 }
-static bool g_tail_split = env_on("MDEMI_GEMM_TAIL_SPLIT");
+static GemmOptions g_opt{env_on("MDEMI_GEMM_TAIL_SPLIT"), 8};  // tail split; raster group_m
 static bool g_inline_reduce = env_set("MDEMI_GEMM_INLINE_REDUCE");
 static bool g_inline_reduce_b16 = env_set("MDEMI_GEMM_INLINE_REDUCE_B16");
-static int g_variant_m16 = -1;  // 16-bit family (bf16 / split fp32): 0 two LDS buffers, 1 one
-static int g_variant_b16 = -1;  // bf16-operand family: 0 128-row tile, 1 256-row tile, 2 128-row x 2 K tiles
-static int g_group_m = 8;
+static int g_variant_m16 = -1;  // 16-bit family (bf16 / split fp32)
+static int g_variant_b16 = -1;  // bf16-operand family
 
 KernelFn f32_pick_part0(int al, int bl, int aop, int bop, int v);
 KernelFn f32_pick_part1(int al, int bl, int aop, int bop, int v);
@@ -141,7 +117,7 @@ KernelFn glds_pick_part0(int al, int bl, int v);
 KernelFn glds_pick_part1(int al, int bl, int v);
 
 static KernelFn pick_kernel(int al, int bl, int aop, int bop, int v) {
-  if (v >= 8) {  // direct-to-LDS variants: dense operands without a load-time op
+  if (F32_VARIANTS[v].dma) {  // direct-to-LDS variants: dense operands without a load-time op
     if (aop != MDEMI_OP_NONE || bop != MDEMI_OP_NONE) return nullptr;
     if (KernelFn f = glds_pick_part0(al, bl, v)) return f;
     return glds_pick_part1(al, bl, v);
@@ -151,25 +127,6 @@ static KernelFn pick_kernel(int al, int bl, int aop, int bop, int v) {
   if (KernelFn f = f32_pick_part2(al, bl, aop, bop, v)) return f;
   return f32_pick_part3(al, bl, aop, bop, v);
 }
-
-static int variant_bk(int v, int mode) {
-  if (mode != GEMM_F32) return 32;  // the 16-bit and bf16-operand families: BK 32
-  if (v >= 8) return (v == 8 || v == 10 || v == 12) ? 32 : 16;
-  return (v >= 3 && v != 7) ? 32 : 16;
-}
-static int variant_cols(int v, int mode) { return (mode == GEMM_F32 && v == 12) ? 192 : GBN; }
-static int variant_rows(int v, int mode) {
-  if (mode == GEMM_B16) return v == 1 ? 2 * GBM : GBM;
-  return (mode != GEMM_F32 ? (v == 2 || v == 4) : (v == 6 || v == 7 || v == 9 || v == 10)) ? 2 * GBM : GBM;
-}
-// the direct-to-LDS variants need dense operands that load as whole 16-B quads and no
-// load-time transform
-static bool glds_ok(const mdemi_gemm_desc* d, const GemmParams& p) {
-  return d->a_layout != MDEMI_L_CONV && d->b_layout != MDEMI_L_CONV && d->a_op == MDEMI_OP_NONE &&
-         d->b_op == MDEMI_OP_NONE && p.a_vec && p.b_vec;
-}
-
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 static int validate(const mdemi_gemm_desc* d) {
   MDEMI_REQUIRE(d, "gemm: null descriptor");
@@ -224,36 +181,7 @@ static int device_cus() {
   return cus[dev];
 }
 
-// Tail split.  A whole-K GEMM whose 128x128 tiles fill R full rounds of resident
-// workgroups plus a thin last round (profiles/round3: 9600x3072x768 = 2.34 rounds of the
-// 3-workgroup/CU variant runs at 115 TF/s vs 130 at exactly 2 or 3 rounds) splits the rows
-// holding the leftover tiles into `split` K pieces, which fit in the last round's free
-// slots, and the last-arriving piece of each tile combines them.  The plan depends on the
-// shape only (rows cut at a 256-row boundary, K at the family's 32-element chunks), so every
-// variant splits the same outputs the same way and the family stays bit-identical.
-struct TailPlan {
-  int m_split, split;  // split 1: no tail split
-};
-static TailPlan tail_plan(const mdemi_gemm_desc* d) {
-  TailPlan t{0, 1};
-  if (!g_tail_split || d->split_k > 1 || d->batch != 1 || d->rowsum_a) return t;
-  const int64_t tm = cdiv(d->M, 128), tn = cdiv(d->N, 128), T = tm * tn;
-  const int64_t S = 3LL * device_cus();  // resident 128x128 tiles (3 workgroups per CU)
-  const int64_t full = T / S, rem = T - full * S;
-  if (full < 1 || rem == 0 || rem * 10 > S * 6) return t;  // no thin last round
-  const int64_t m_split = (tm - cdiv(rem, tn)) / 2 * 256;
-  if (m_split <= 0) return t;
-  const int64_t tail_tiles = cdiv(d->M - m_split, 128) * tn;
-  int64_t s = std::min<int64_t>(4, S / tail_tiles);
-  s = std::min<int64_t>(s, cdiv(d->K, 32) / 2);  // every piece keeps >= 2 K chunks
-  if (s < 2) return t;
-  t.m_split = (int)m_split;
-  t.split = (int)s;
-  return t;
-}
-
-static void fill_params(const mdemi_gemm_desc* d, GemmParams& p, int variant, int mode) {
-  const int GBK = variant_bk(variant, mode);
+static void fill_params(const mdemi_gemm_desc* d, const GemmPlan& pl, GemmParams& p) {
   p.M = d->M; p.N = d->N; p.K = d->K; p.batch = d->batch;
   p.A = d->A; p.lda = d->lda; p.a_bs = d->a_bstride;
   p.B = d->B; p.ldb = d->ldb; p.b_bs = d->b_bstride;
@@ -271,47 +199,20 @@ static void fill_params(const mdemi_gemm_desc* d, GemmParams& p, int variant, in
   p.a_bs2 = p.binner > 1 ? d->a_bstride_inner : 0;
   p.b_bs2 = p.binner > 1 ? d->b_bstride_inner : 0;
   p.c_bs2 = p.binner > 1 ? d->c_bstride_inner : 0;
-  // split boundaries in fixed 32-element K chunks whatever the variant's BK, so the
-  // variants of a family agree bit for bit
-  const int CH = 32;
-  const int kc = (int)cdiv(d->K, CH);
-  const TailPlan tp = tail_plan(d);
-  const int want = tp.split > 1 ? tp.split : d->split_k;
-  const int split = want < kc ? want : kc;
-  const int chunks_per_split = (int)cdiv(kc, split);
-  p.ktile_per_split = chunks_per_split * (CH / GBK);
-  p.split = (int)cdiv(kc, chunks_per_split);
-  p.m_split = (tp.split > 1 && p.split > 1) ? tp.m_split : 0;
-  p.tile_cnt = nullptr;
-  p.rowsum_out = nullptr;
-  p.c16 = nullptr;
-  // vector loads need every row start 16-B aligned and whole quads in range
-  // (KCONTIG: K % 4; MNCONTIG: the row/column extent % 4)
-  p.a_vec = al16(d->A) && (d->lda % 4 == 0) && (d->a_bstride % 4 == 0) && (p.a_bs2 % 4 == 0) &&
-            (d->a_layout == MDEMI_L_KCONTIG ? d->K % 4 == 0 : d->M % 4 == 0);
-  p.b_vec = al16(d->B) && (d->ldb % 4 == 0) && (d->b_bstride % 4 == 0) && (p.b_bs2 % 4 == 0) &&
-            (d->b_layout == MDEMI_L_KCONTIG ? d->K % 4 == 0 : d->N % 4 == 0);
+  p.split = pl.split; p.ktile_per_split = pl.ktile_per_split; p.m_split = pl.m_split;
+  p.tiles_m1 = pl.tiles_m1; p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.group_m = pl.group_m;
+  p.slab = nullptr; p.tile_cnt = nullptr; p.rowsum_out = nullptr; p.c16 = nullptr;
+  p.a_vec = a_vec(d); p.b_vec = b_vec(d);
   if (d->a_layout == MDEMI_L_CONV || d->b_layout == MDEMI_L_CONV) {
     const mdemi_conv_geom& g = d->conv;
     p.fd_c = make_fastdiv(g.c); p.fd_kw = make_fastdiv(g.kw);
     p.fd_ow = make_fastdiv(g.ow); p.fd_oh = make_fastdiv(g.oh);
   }
-  p.slab = nullptr;
-  const int vrows = variant_rows(variant, mode);  // 256-row variants: 16-bit 2, fp32 6 and 7
-  p.tiles_m1 = p.m_split / vrows;
-  p.tiles_m = (int)cdiv(d->M - p.m_split, vrows);
-  p.tiles_n = (int)cdiv(d->N, variant_cols(variant, mode));
-  p.group_m = g_group_m;
 }
 
 }  // namespace mdemi
 
 using namespace mdemi;
-
-static size_t slab_bytes(const mdemi_gemm_desc* d, const GemmParams& p) {
-  return p.split > 1 ? align_up((size_t)p.split * d->batch * (size_t)(d->M - p.m_split) * d->N * sizeof(float), 256)
-                     : 0;
-}
 
 // Per-device split-tile counters for the in-kernel slab combine: zeroed once on the
 // launch stream, left zeroed by every launch (the last arriver resets its tile's slot).
@@ -336,17 +237,15 @@ static int* tile_counters(int64_t n, hipStream_t st) {
   e = {ptr, cap};
   return ptr;
 }
-static size_t rowsum_bytes(const mdemi_gemm_desc* d, const GemmParams& p) {
-  return (p.split > 1 && d->rowsum_a) ? (size_t)p.split * d->M * sizeof(float) : 0;
+// The plan under the process's options; the device is asked for its CU count only where
+// the tail split can apply.
+static GemmPlan plan_for(const mdemi_gemm_desc* d, int mode, int variant) {
+  const bool tail = g_opt.tail_split && tail_split_shape(d);
+  return plan_gemm(d, mode, variant, tail ? device_cus() : 0, GemmOptions{tail, g_opt.group_m});
 }
-
-// split-K combine by column sums: deep splits with a plain store epilogue
-static bool colsum_combine(const mdemi_gemm_desc* d, const GemmParams& p) {
-  return p.split >= 32 && d->batch == 1 && d->alpha == 1.f && d->beta == 0.f && d->bias_mode == MDEMI_BIAS_NONE &&
-         d->act == MDEMI_ACT_NONE && !d->residual && !d->preact && d->ldc == d->N;
-}
-static size_t colsum_combine_bytes(const mdemi_gemm_desc* d, const GemmParams& p) {
-  return colsum_combine(d, p) ? colsum_ws_bytes(p.split, (int64_t)d->M * d->N) : 0;
+// workspace of a split plan: slabs, row-sum partials, then the deep combine's column-sum scratch
+static size_t plan_bytes(const mdemi_gemm_desc* d, const GemmPlan& g) {
+  return g.slab_bytes + g.rowsum_bytes + (g.deep ? colsum_ws_bytes(g.split, (int64_t)d->M * d->N) : 0);
 }
 
 // bf16 operands / output of mdemi_gemm_bf16x (null for the fp32-operand entry points)
@@ -355,12 +254,7 @@ struct B16Ext {
 };
 
 static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mode, const B16Ext* ext = nullptr) {
-  if (mode == GEMM_F32E && variant >= 3) variant = 0;  // the bf16-image variants hold one bf16 plane
-  if (mode == GEMM_F32 && variant >= 8) {  // a forced direct-to-LDS variant on an operand it cannot stage
-    GemmParams q;
-    fill_params(d, q, variant, mode);
-    if (!glds_ok(d, q)) variant = 0;
-  }
+  variant = resolve_variant(d, mode, variant);
   KernelFn fn = mode == GEMM_F32   ? pick_kernel(d->a_layout, d->b_layout, d->a_op, d->b_op, variant)
                 : mode == GEMM_B16 ? pick_kernel_b16(d->a_layout, d->b_layout, variant)
                                    : pick_kernel_m16(d->a_layout, d->b_layout, d->a_op, d->b_op,
@@ -370,8 +264,9 @@ static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mod
               d->b_op);
     return MDEMI_EUNSUP;
   }
+  const GemmPlan g = plan_for(d, mode, variant);
   GemmParams p;
-  fill_params(d, p, variant, mode);
+  fill_params(d, g, p);
   if (ext) {
     p.c16 = ext->c16;
     if (mode == GEMM_B16) {  // the kernel reads the bf16 tensors through the A/B slots
@@ -381,20 +276,19 @@ static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mod
   }
   float* rowsum_part = nullptr;
   if (p.split > 1) {
-    const size_t need = slab_bytes(d, p) + rowsum_bytes(d, p) + colsum_combine_bytes(d, p);
+    const size_t need = plan_bytes(d, g);
     if (!d->workspace || (size_t)d->workspace_bytes < need) {
       set_error("gemm: split-K needs %zu workspace bytes", need);
       return MDEMI_EWORKSPACE;
     }
     p.slab = (float*)d->workspace;
     if (d->rowsum_a) {
-      rowsum_part = (float*)((char*)d->workspace + slab_bytes(d, p));
+      rowsum_part = (float*)((char*)d->workspace + g.slab_bytes);
       p.rowsum = rowsum_part;
     }
   }
-  const int64_t nblocks = (int64_t)p.tiles_m1 * p.tiles_n + (int64_t)p.tiles_m * p.tiles_n * d->batch * p.split;
-  MDEMI_REQUIRE(nblocks < (int64_t)1 << 31, "gemm: grid too large");
-  const bool deep = p.split > 1 && colsum_combine(d, p) && !p.c16;  // the column-sum combine writes fp32 only
+  MDEMI_REQUIRE(g.nblocks < (int64_t)1 << 31, "gemm: grid too large");
+  const bool deep = g.deep && !p.c16;  // the column-sum combine writes fp32 only
   // both bf16 families (bf16 operands in HBM, or rounded at staging) combine alike, so the
   // bf16-storage step stays bit-identical to the fp32-operand bf16 step
   const bool inline_reduce = (mode == GEMM_B16 || mode == GEMM_BF16) ? g_inline_reduce_b16 : g_inline_reduce;
@@ -402,13 +296,13 @@ static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mod
     p.tile_cnt = tile_counters((int64_t)p.tiles_m * p.tiles_n * d->batch, st);
     if (p.tile_cnt && rowsum_part) p.rowsum_out = d->rowsum_a;  // the last arrivers sum the row partials
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)nblocks), dim3(GTHREADS), 0, st, p);
+  hipLaunchKernelGGL(fn, dim3((unsigned)g.nblocks), dim3(GTHREADS), 0, st, p);
   if (p.split > 1 && !p.tile_cnt) {
     if (deep) {
       // many slabs over a small C (skinny weight gradients over ~10^6 pixels): a
       // column sum parallel over the slab rows, not one thread per output summing
       // `split` dependent loads
-      char* cws = (char*)d->workspace + slab_bytes(d, p) + rowsum_bytes(d, p);
+      char* cws = (char*)d->workspace + g.slab_bytes + g.rowsum_bytes;
       int rc = colsum_launch(p.slab, p.split, (int64_t)d->M * d->N, (int64_t)d->M * d->N, d->C, 0, cws, st);
       if (!rc && rowsum_part) rc = colsum_launch(rowsum_part, p.split, d->M, d->M, d->rowsum_a, 0, cws, st);
       if (rc) return rc;
@@ -444,11 +338,8 @@ static bool tunable(const mdemi_gemm_desc* d, hipStream_t st) {
 }
 
 static int choose_variant(const mdemi_gemm_desc* d, hipStream_t st, int mode, const B16Ext* ext = nullptr) {
-  if (mode == GEMM_B16) {
-    if (g_variant_b16 >= 0) return g_variant_b16;
-  } else if (mode != GEMM_F32 ? g_variant_m16 >= 0 : g_variant >= 0) {
-    return mode != GEMM_F32 ? g_variant_m16 : g_variant;
-  }
+  const int forced = mode == GEMM_F32 ? g_variant : mode == GEMM_B16 ? g_variant_b16 : g_variant_m16;
+  if (forced >= 0) return forced;
   const TuneKey key{d->a_layout, d->b_layout, d->a_op, d->b_op, d->M, d->N, d->K, d->batch, d->split_k, mode};
   {
     std::lock_guard<std::mutex> lk(g_tune_mu);
@@ -457,21 +348,12 @@ static int choose_variant(const mdemi_gemm_desc* d, hipStream_t st, int mode, co
   }
   if (!tunable(d, st)) return 0;
   if (ext && ext->c16 && (ext->c16 == ext->a16 || ext->c16 == ext->b16)) return 0;
-  static const int cands_f32[] = {0, 1, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12};
-  static const int cands_m16[] = {0, 1, 2, 3, 4};
-  const int* cands = mode != GEMM_F32 ? cands_m16 : cands_f32;
-  int ncand = mode == GEMM_BF16 ? 5 : mode == GEMM_F32E ? 3 : mode == GEMM_B16 ? 3 : 12;
-  if (mode == GEMM_F32) {
-    GemmParams q;
-    fill_params(d, q, 0, mode);
-    if (!glds_ok(d, q)) ncand = 7;
-  }
   hipEvent_t e0, e1;
   if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 0;
   int best = 0;
   float best_ms = 1e30f;
-  for (int ci = 0; ci < ncand; ++ci) {
-    const int v = cands[ci];
+  for (int v = 0; v < variant_table(mode).n; ++v) {
+    if (!tune_candidate(d, mode, v)) continue;
     if (launch(d, v, st, mode, ext) != MDEMI_OK) continue;  // warm (and validate)
     (void)hipEventRecord(e0, st);
     for (int r = 0; r < 3; ++r) launch(d, v, st, mode, ext);
@@ -489,10 +371,8 @@ static int choose_variant(const mdemi_gemm_desc* d, hipStream_t st, int mode, co
 
 extern "C" size_t mdemi_gemm_workspace_size(const mdemi_gemm_desc* d) {
   if (!d) return 0;
-  GemmParams p;
-  fill_params(d, p, 0, GEMM_F32);  // every family splits at the same 32-element chunks
-  if (p.split <= 1) return 0;
-  return slab_bytes(d, p) + rowsum_bytes(d, p) + colsum_combine_bytes(d, p);
+  // every variant of every family splits at the same 32-element chunks
+  return plan_bytes(d, plan_for(d, GEMM_F32, 0));
 }
 
 static int gemm_entry(const mdemi_gemm_desc* d, void* stream, int mode) {
@@ -506,9 +386,8 @@ static int gemm_entry(const mdemi_gemm_desc* d, void* stream, int mode) {
 // quads of 8 bf16: k-contiguous K % 8, m/n-contiguous extent % 8, implicit-im2col C % 8,
 // leading dimensions and batch strides % 8, 16-B aligned bases, no load-time op, no
 // bias-gradient row sums -- those are summed from the unrounded fp32 operand)
-static bool al16v(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static bool b16_ok(const mdemi_gemm_desc* d, const B16Ext& e) {
-  if (!e.a16 || !e.b16 || !al16v(e.a16) || !al16v(e.b16)) return false;
+  if (!e.a16 || !e.b16 || !al16(e.a16) || !al16(e.b16)) return false;
   if (d->a_op != MDEMI_OP_NONE || d->b_op != MDEMI_OP_NONE || d->rowsum_a) return false;
   if (d->a_layout == MDEMI_L_CONV && d->b_layout == MDEMI_L_CONV) return false;
   auto operand = [&](int layout, int64_t ld, int64_t bs, int64_t bs2, int64_t extent) {
@@ -553,31 +432,30 @@ extern "C" int mdemi_gemm_f32(const mdemi_gemm_desc* d, void* stream) { return g
 extern "C" int mdemi_gemm_bf16(const mdemi_gemm_desc* d, void* stream) { return gemm_entry(d, stream, GEMM_BF16); }
 extern "C" int mdemi_gemm_f32e(const mdemi_gemm_desc* d, void* stream) { return gemm_entry(d, stream, GEMM_F32E); }
 
-// Benchmark/tuning hook: force a pipelining variant of the fp32 family (see
-// pick_variant) and of the 16-bit family (gemm_mfma16.hip m16_variant; -1 =
-// per-shape autotune, the default) and the tile raster (group_m > 0: XCD-aware
-// grouped raster; 0: plain).
+// Benchmark/tuning hooks: force a variant of a family (an index of its table in
+// gemm_plan.h; -1 = per-shape autotune, the default) and the tile raster (group_m > 0:
+// XCD-aware grouped raster; 0: plain).
 extern "C" int mdemi_gemm_set_variant(int32_t variant, int32_t group_m) {
-  MDEMI_REQUIRE(variant >= -1 && variant < NVARIANTS && group_m >= 0, "gemm_set_variant: bad args");
+  MDEMI_REQUIRE(variant >= -1 && variant < variant_table(GEMM_F32).n && group_m >= 0, "gemm_set_variant: bad args");
   g_variant = variant;
-  g_group_m = group_m;
+  g_opt.group_m = group_m;
   return MDEMI_OK;
 }
 
 extern "C" int mdemi_gemm_set_options(int32_t tail_split, int32_t inline_reduce) {
-  g_tail_split = tail_split != 0;
+  g_opt.tail_split = tail_split != 0;
   g_inline_reduce = inline_reduce != 0;
   return MDEMI_OK;
 }
 
 extern "C" int mdemi_gemm_set_variant_m16(int32_t variant) {
-  MDEMI_REQUIRE(variant >= -1 && variant < 5, "gemm_set_variant_m16: bad variant");
+  MDEMI_REQUIRE(variant >= -1 && variant < variant_table(GEMM_BF16).n, "gemm_set_variant_m16: bad variant");
   g_variant_m16 = variant;
   return MDEMI_OK;
 }
 
 extern "C" int mdemi_gemm_set_variant_b16(int32_t variant) {
-  MDEMI_REQUIRE(variant >= -1 && variant < 3, "gemm_set_variant_b16: bad variant");
+  MDEMI_REQUIRE(variant >= -1 && variant < variant_table(GEMM_B16).n, "gemm_set_variant_b16: bad variant");
   g_variant_b16 = variant;
   return MDEMI_OK;
 }

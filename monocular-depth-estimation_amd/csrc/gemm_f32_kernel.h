@@ -15,7 +15,7 @@ using KernelFn = void (*)(GemmParams);
 //   PREF  register prefetch of the next tile before the MFMAs (issue early / write late)
 //   BMT   block-tile rows: 128 (2x2 waves of 64x64) or 256 (2x2 waves of 128x64, A staged as
 //         two 128-row images: twice the MFMAs per barrier and per B fragment)
-// Variants 8..11 stage by DMA straight into LDS (gemm_glds_kernel.h).
+// The table's dma variants stage straight into LDS (gemm_glds_kernel.h).
 template <int AL, int BL, int AOP, int BOP, int BK, int NBUF, bool PREF, bool TR, int OCC, int BMT = 128>
 __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8))) void gemm_f32_kernel(GemmParams p) {
   using LA = Loader<AL, AOP, true, BK, TR>;
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
 
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-  const GemmJob job = job_of(p);
+  const GemmJob job = job_of(p, blockIdx.x);
   const int b = job.b, sidx = job.sidx, tm = job.tm, tn = job.tn;
   const int bm = tm * BMT, bn = tn * GBN;
 
@@ -177,16 +177,18 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
 
 template <int AL, int BL, int AOP, int BOP>
 static KernelFn pick_variant(int v) {
-  if (v >= 8) return nullptr;  // direct-to-LDS staging: gemm_glds_inst*.hip (gemm_f32.hip pick_kernel)
+  constexpr const GemmVariant* T = F32_VARIANTS;  // tile rows and BK: the host's table (gemm_plan.h)
+  static_assert(tiles_fixed(F32_VARIANTS, false, GBN), "this kernel's tiles are GBN columns wide");
   switch (v) {
-    case 1: return gemm_f32_kernel<AL, BL, AOP, BOP, 16, 2, true, false, 2>;
-    case 2: return gemm_f32_kernel<AL, BL, AOP, BOP, 16, 2, true, true, 4>;
-    case 3: return gemm_f32_kernel<AL, BL, AOP, BOP, 32, 2, true, true, 2>;
-    case 4: return gemm_f32_kernel<AL, BL, AOP, BOP, 32, 1, true, true, 3>;
-    case 5: return gemm_f32_kernel<AL, BL, AOP, BOP, 32, 2, true, false, 2>;
-    case 6: return gemm_f32_kernel<AL, BL, AOP, BOP, 32, 1, true, true, 2, 256>;
-    case 7: return gemm_f32_kernel<AL, BL, AOP, BOP, 16, 2, true, true, 2, 256>;
-    default: return gemm_f32_kernel<AL, BL, AOP, BOP, 16, 2, true, true, 2>;
+    case 1: return gemm_f32_kernel<AL, BL, AOP, BOP, T[1].bk, 2, true, false, 2, T[1].rows>;
+    case 2: return gemm_f32_kernel<AL, BL, AOP, BOP, T[2].bk, 2, true, true, 4, T[2].rows>;
+    case 3: return gemm_f32_kernel<AL, BL, AOP, BOP, T[3].bk, 2, true, true, 2, T[3].rows>;
+    case 4: return gemm_f32_kernel<AL, BL, AOP, BOP, T[4].bk, 1, true, true, 3, T[4].rows>;
+    case 5: return gemm_f32_kernel<AL, BL, AOP, BOP, T[5].bk, 2, true, false, 2, T[5].rows>;
+    case 6: return gemm_f32_kernel<AL, BL, AOP, BOP, T[6].bk, 1, true, true, 2, T[6].rows>;
+    case 7: return gemm_f32_kernel<AL, BL, AOP, BOP, T[7].bk, 2, true, true, 2, T[7].rows>;
+    case 0: return gemm_f32_kernel<AL, BL, AOP, BOP, T[0].bk, 2, true, true, 2, T[0].rows>;
+    default: return nullptr;  // direct-to-LDS staging: gemm_glds_inst*.hip (gemm_f32.hip pick_kernel)
   }
 }
 

@@ -1,5 +1,5 @@
 // fp32 MFMA GEMM with direct-to-LDS operand staging (gfx950 `buffer_load_dwordx4 ... lds`):
-// the pipelining variants 8..11 of the fp32 family (gemm_f32_kernel.h pick_variant) for
+// the dma variants of the fp32 family (F32_VARIANTS in gemm_plan.h; pick_glds below) for
 // dense operands (k-contiguous or m/n-contiguous, 16-B vectorisable, no load-time op).
 //
 // Why: the register-staged kernel spends its issue slots and VGPRs on the global loads, the
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wid >> 1, wn = wid & 1;
-  const GemmJob job = job_of(p);
+  const GemmJob job = job_of(p, blockIdx.x);
   const int b = job.b, sidx = job.sidx, tm = job.tm, tn = job.tn;
   const int bm = tm * BMT, bn = tn * BNT;
 
@@ -302,18 +302,19 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
 #include "gemm_epilogue.inc"
 }
 
-// variants 8..12 (gemm_f32.hip pick_kernel), instantiated per layout pair in gemm_glds_inst*.hip
+// the dma variants of F32_VARIANTS (gemm_f32.hip pick_kernel), instantiated per layout pair in gemm_glds_inst*.hip
 template <int AL, int BL>
 static void (*pick_glds(int v))(GemmParams) {
   if constexpr (AL == MDEMI_L_CONV || BL == MDEMI_L_CONV) {
     return nullptr;
   } else {
+    constexpr const GemmVariant* T = F32_VARIANTS;  // the tile: the host's table (gemm_plan.h)
     switch (v) {
-      case 8: return gemm_glds_kernel<AL, BL, 128, 32, 2>;
-      case 9: return gemm_glds_kernel<AL, BL, 256, 16, 2>;
-      case 10: return gemm_glds_kernel<AL, BL, 256, 32, 1>;
-      case 11: return gemm_glds_kernel<AL, BL, 128, 16, 3>;
-      case 12: return gemm_glds_kernel<AL, BL, 128, 32, 2, 192>;
+      case 8: return gemm_glds_kernel<AL, BL, T[8].rows, T[8].bk, 2, T[8].cols>;
+      case 9: return gemm_glds_kernel<AL, BL, T[9].rows, T[9].bk, 2, T[9].cols>;
+      case 10: return gemm_glds_kernel<AL, BL, T[10].rows, T[10].bk, 1, T[10].cols>;
+      case 11: return gemm_glds_kernel<AL, BL, T[11].rows, T[11].bk, 3, T[11].cols>;
+      case 12: return gemm_glds_kernel<AL, BL, T[12].rows, T[12].bk, 2, T[12].cols>;
       default: return nullptr;
     }
   }

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(GTHREADS) void gemm_m16_kernel(GemmParams p) {
 
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   const int wm = wid >> 1, wn = wid & 1;
-  const GemmJob job = job_of(p);
+  const GemmJob job = job_of(p, blockIdx.x);
   const int b = job.b, sidx = job.sidx, tm = job.tm, tn = job.tn;
   const int bm = tm * BMT, bn = tn * GBN;
 
@@ -314,22 +314,26 @@ __global__ __launch_bounds__(GTHREADS) void gemm_m16_kernel(GemmParams p) {
 
 using KernelFn16 = void (*)(GemmParams);
 
-// 16-bit family variants: 0 = 128-row tile, two LDS buffers; 1 = 128-row tile, one
-// buffer (two workgroups per CU by LDS); 2 = 256-row tile, two buffers (96 KiB);
-// 3 / 4 = bf16 LDS images (bf16 only), 128- / 256-row tile, two buffers (32 / 48 KiB).
+// 16-bit family variants (M16_VARIANTS, gemm_plan.h: the tile rows come from there): LDS
+// buffers and, for 3 / 4, bf16 LDS images (one plane: NP = 1 only).
 // Every variant adds each output's products in the same order (bit-identical).
 template <int AL, int BL, int AOP, int BOP>
 static KernelFn16 m16_variant(int np, int v) {
-  if (v >= 3) {  // bf16 LDS images (NP = 1): 3 = 128-row tile, 4 = 256-row tile, two buffers each
-    if (np != 1) return nullptr;
-    return v == 4 ? gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, 256, true> : gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, 128, true>;
+  constexpr const GemmVariant* T = M16_VARIANTS;
+  static_assert(tiles_fixed(M16_VARIANTS, false, GBN, M16_BK), "this kernel's tiles are GBN x M16_BK");
+  if (np == 3) switch (v) {
+      case 1: return gemm_m16_kernel<AL, BL, AOP, BOP, 3, 1, T[1].rows>;
+      case 2: return gemm_m16_kernel<AL, BL, AOP, BOP, 3, 2, T[2].rows>;
+      case 3: case 4: return nullptr;
+      default: return gemm_m16_kernel<AL, BL, AOP, BOP, 3, 2, T[0].rows>;
+    }
+  switch (v) {
+    case 1: return gemm_m16_kernel<AL, BL, AOP, BOP, 1, 1, T[1].rows>;
+    case 2: return gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, T[2].rows>;
+    case 3: return gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, T[3].rows, true>;
+    case 4: return gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, T[4].rows, true>;
+    default: return gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, T[0].rows>;
   }
-  if (np == 3) {
-    if (v == 2) return gemm_m16_kernel<AL, BL, AOP, BOP, 3, 2, 256>;
-    return v == 1 ? gemm_m16_kernel<AL, BL, AOP, BOP, 3, 1, 128> : gemm_m16_kernel<AL, BL, AOP, BOP, 3, 2, 128>;
-  }
-  if (v == 2) return gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, 256>;
-  return v == 1 ? gemm_m16_kernel<AL, BL, AOP, BOP, 1, 1, 128> : gemm_m16_kernel<AL, BL, AOP, BOP, 1, 2, 128>;
 }
 template <int AL, int BL>
 static KernelFn16 m16_ops(int aop, int bop, int np, int v) {

@@ -1,45 +1,19 @@
-"""Host restatement of the GEMM workgroup -> job map (csrc/gemm_core.h: xcd_lin, tile_of,
-job_of) checked for being a bijection: every (batch entry, K piece, row tile, column tile)
-job is computed by exactly one workgroup for any grid the launcher builds
-(gemm_f32.hip launch: n1 whole-K tiles + tiles_m * tiles_n * batch * split split jobs), and
-every tile of one K piece sits on one XCD (workgroup id mod 8) except where the XCD ranges
-cut the job list."""
+"""The GEMM workgroup -> job map (csrc/gemm_plan.h: xcd_lin, tile_of, job_of -- the text the
+kernels compile, run on the host by tests/gemm_plan_probe.cpp) checked for being a bijection:
+every (batch entry, K piece, row tile, column tile) job is computed by exactly one workgroup
+for any grid the launcher builds (plan_gemm: n1 whole-K tiles + tiles_m * tiles_n * batch *
+split split jobs), and every tile of one K piece sits on one XCD (workgroup id mod 8) except
+where the XCD ranges cut the job list."""
 import itertools
 
 import pytest
 
-
-def xcd_lin(bid, n):
-    q, r = divmod(n, 8)
-    xcd, idx = bid % 8, bid // 8
-    return (xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q) + idx
+from gemm_plan_util import probe
 
 
-def tile_of(bid, ntiles, tiles_m, tiles_n, group_m, remap=True):
-    if group_m <= 0:
-        return bid // tiles_n, bid % tiles_n
-    lin = xcd_lin(bid, ntiles) if remap else bid
-    per_group = group_m * tiles_n
-    grp = lin // per_group
-    first_m = grp * group_m
-    gm = min(tiles_m - first_m, group_m)
-    in_grp = lin % per_group
-    return first_m + in_grp % gm, in_grp // gm
-
-
-def job_of(bid, tiles_m1, tiles_m, tiles_n, batch, split, group_m):
-    n1 = tiles_m1 * tiles_n
-    if bid < n1:
-        tm, tn = tile_of(bid, n1, tiles_m1, tiles_n, group_m)
-        return (0, 0, tm, tn)
-    bid -= n1
-    n2 = tiles_m * tiles_n
-    if group_m > 0:
-        bid = xcd_lin(bid, n2 * batch * split)
-    zb, t2 = divmod(bid, n2)
-    b, sidx = divmod(zb, split)
-    tm2, tn = tile_of(t2, n2, tiles_m, tiles_n, group_m, remap=False)
-    return (b, sidx, tiles_m1 + tm2, tn)
+def jobs_of(tiles_m1, tiles_m, tiles_n, batch, split, group_m):
+    """(b, sidx, tm, tn) of every workgroup id, in launch order."""
+    return [tuple(r) for r in probe("jobs", tiles_m1, tiles_m, tiles_n, batch, split, group_m)]
 
 
 SHAPES = [  # (tiles_m1, tiles_m, tiles_n, batch, split)
@@ -53,7 +27,7 @@ SHAPES = [  # (tiles_m1, tiles_m, tiles_n, batch, split)
 def test_job_map_is_a_bijection(shape, group_m):
     tiles_m1, tiles_m, tiles_n, batch, split = shape
     nblocks = tiles_m1 * tiles_n + tiles_m * tiles_n * batch * split
-    jobs = [job_of(b, tiles_m1, tiles_m, tiles_n, batch, split, group_m) for b in range(nblocks)]
+    jobs = jobs_of(tiles_m1, tiles_m, tiles_n, batch, split, group_m)
     expect = {(0, 0, tm, tn) for tm, tn in itertools.product(range(tiles_m1), range(tiles_n))}
     expect |= {(b, s, tiles_m1 + tm, tn) for b, s, tm, tn in
                itertools.product(range(batch), range(split), range(tiles_m), range(tiles_n))}
@@ -64,7 +38,8 @@ def test_split_pieces_stay_on_one_xcd():
     # wgrad-like: 2 x 18 tiles, 64 K pieces -> each XCD owns 8 whole pieces
     tiles_m, tiles_n, split = 2, 18, 64
     xcd_of = {}
-    for bid in range(tiles_m * tiles_n * split):
-        _, s, _, _ = job_of(bid, 0, tiles_m, tiles_n, 1, split, 8)
+    jobs = jobs_of(0, tiles_m, tiles_n, 1, split, 8)
+    assert len(jobs) == tiles_m * tiles_n * split
+    for bid, (_, s, _, _) in enumerate(jobs):
         xcd_of.setdefault(s, set()).add(bid % 8)
     assert all(len(x) == 1 for x in xcd_of.values())

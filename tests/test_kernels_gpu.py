@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gemm_plan_util import tail_plan_m_split as _tail_plan_m_split
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -651,7 +653,7 @@ def test_gemm_variants_bit_identical(mf, layouts):
 
 @pytest.mark.parametrize("layouts", ["fwd", "dgrad"])
 def test_gemm_tail_split(mf, layouts):
-    """Tail split (gemm_f32.hip tail_plan): 9600x3072x768 leaves a thin third round of
+    """Tail split (tail_plan in csrc/gemm_plan.h): 9600x3072x768 leaves a thin third round of
     128x128 tiles, so the rows holding them are cut at a 256-row boundary and split over K
     (combined by the last-arriving piece).  Every variant must agree bit for bit with the
     split on; rows above the cut equal the unsplit result bit for bit; all within the fp32
@@ -694,23 +696,6 @@ def test_gemm_tail_split(mf, layouts):
     c = outs[0][1]
     assert torch.equal(c[:m_split], plain[:m_split]), "rows above the cut must be the unsplit result"
     assert not torch.equal(c[m_split:], plain[m_split:]), "tail rows were not split (plan did not engage)"
-
-
-def _tail_plan_m_split(M, N, K, cus):
-    """Host restatement of gemm_f32.hip tail_plan (batch 1, split_k 1): the first split row,
-    0 when the plan does not engage.  The plan depends on the device's CU count, so which rows
-    are split over K -- and hence their fp32 summation order -- differs between GPU SKUs."""
-    cdiv = lambda a, b: -(-a // b)  # noqa: E731
-    tm, tn = cdiv(M, 128), cdiv(N, 128)
-    T, S = tm * tn, 3 * cus
-    full, rem = T // S, T % S
-    if full < 1 or rem == 0 or rem * 10 > S * 6:
-        return 0
-    m_split = (tm - cdiv(rem, tn)) // 2 * 256
-    if m_split <= 0:
-        return 0
-    s = min(4, S // (cdiv(M - m_split, 128) * tn), cdiv(K, 32) // 2)
-    return m_split if s >= 2 else 0
 
 
 @pytest.mark.parametrize("layouts", ["fwd", "wgrad"])

@@ -383,6 +383,45 @@ int mdemi_adamw_step_dev_guarded16(const mdemi_tensor_ref* tensors_dev, int32_t 
                                    float grad_scale, int64_t nitems, void* const* param16_dev,
                                    mdemi_guard_state* guard_dev, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* AdamW steps that also keep an exponential moving average of the weights   */
+/* (train.ema_decay): mdemi_adamw_step16 / mdemi_adamw_step_dev16 with the   */
+/* average updated in the same sweep, on the value just written to param:    */
+/*   n = ema_state_dev->updates            (read before the tick)            */
+/*   d = ema_warmup ? min(ema_decay, (1 + n) / (10 + n)) : ema_decay  (fp32) */
+/*   e = fmaf(1 - d, p_new - e, e)                                           */
+/* ema_dev: ntensors device pointers in device memory, one per table entry;  */
+/* a NULL entry means that tensor keeps no average.  An average that is not  */
+/* 16-byte aligned is read and written one float at a time; it does not      */
+/* change which path param, exp_avg and exp_avg_sq take, so those stay bit   */
+/* for bit what the step without an average writes.                          */
+/* ema_state_dev points at one mdemi_ema_state in device memory              */
+/* (the host zero-initialises it); the trailing tick kernel adds one to      */
+/* `updates` per applied call.                                               */
+/* guard_dev NULL: p, m, v, the bf16 copies, tensor_steps and *step_dev are  */
+/* written exactly as by mdemi_adamw_step16 / mdemi_adamw_step_dev16.        */
+/* guard_dev non-NULL: exactly as by the guarded entry points above, with    */
+/* their requirements (sumsq, tensor_steps); `step` is not read.  A skipped  */
+/* call writes no byte of any average and leaves `updates` alone.            */
+/* ema_dev or ema_state_dev NULL, or ema_decay outside [0, 1), gives         */
+/* MDEMI_EINVAL and nothing is launched.                                     */
+/* ------------------------------------------------------------------------ */
+typedef struct mdemi_ema_state {
+  int32_t updates; /* applied calls so far */
+} mdemi_ema_state;
+int mdemi_adamw_step_ema16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                           const mdemi_adamw_group* groups_host, int32_t ngroups, const float* sumsq, float max_norm,
+                           float grad_scale, int32_t step, int32_t* tensor_steps, int64_t nitems,
+                           void* const* param16_dev, float* const* ema_dev, float ema_decay, int32_t ema_warmup,
+                           mdemi_ema_state* ema_state_dev, mdemi_guard_state* guard_dev, void* workspace,
+                           void* stream);
+int mdemi_adamw_step_dev_ema16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                               const mdemi_adamw_group* sched_dev, int32_t nsteps, int32_t ngroups,
+                               int32_t* step_dev, int32_t* tensor_steps, const float* sumsq, float max_norm,
+                               float grad_scale, int64_t nitems, void* const* param16_dev, float* const* ema_dev,
+                               float ema_decay, int32_t ema_warmup, mdemi_ema_state* ema_state_dev,
+                               mdemi_guard_state* guard_dev, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

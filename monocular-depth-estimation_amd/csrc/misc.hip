@@ -180,11 +180,19 @@ __global__ void sumsq_final(const float* __restrict__ part, int nitems, float* _
 // non-amsgrad, foreach=False semantics); `step` is the 1-based step count
 // p16 (optional): also write the RNE bf16 copy of the updated parameter -- the operand
 // its bf16 GEMMs read next step (what mdemi_cast_bf16 would produce, bit for bit)
+// EMA, ema (optional): the running average of the parameter, e += (1 - ed) * (p_new - e) on
+// the value just written to param; one more 4-B read and write per element of the same sweep.
+// The float4 body and the scalar tail contract upd() differently (the body is packed fp32
+// math), so the average never decides which of the two a parameter element takes: p, m and v
+// are what the step without an average writes.  An average that is not 16-B aligned is read and
+// written one float at a time inside the float4 body instead.
 typedef __bf16 opt_bf16x4_t __attribute__((ext_vector_type(4)));
 typedef float opt_f32x4_t __attribute__((ext_vector_type(4)));
+template <bool EMA = false>
 __device__ __forceinline__ void adamw_item(const mdemi_tensor_ref& t, const mdemi_adamw_group& gp, float clip,
                                            float gs, float step, int64_t beg, int64_t end,
-                                           __bf16* __restrict__ p16 = nullptr) {
+                                           __bf16* __restrict__ p16 = nullptr, float* __restrict__ ema = nullptr,
+                                           float ed = 0.f) {
   const float b1 = gp.beta1, b2 = gp.beta2;
   const float step_size = gp.lr / (1.f - powf(b1, step));
   const float bc2s = sqrtf(1.f - powf(b2, step));
@@ -199,6 +207,8 @@ __device__ __forceinline__ void adamw_item(const mdemi_tensor_ref& t, const mdem
   };
   const bool vec = (((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq) & 15) == 0 &&
                    ((uintptr_t)p16 & 7) == 0;
+  const bool evec = ((uintptr_t)ema & 15) == 0;
+  const float omd = 1.f - ed;
   const int64_t vend = vec ? beg + ((end - beg) & ~(int64_t)3) : beg;
   for (int64_t i = beg + 4 * threadIdx.x; i < vend; i += 4 * OPT_THREADS) {
     const float4 g = *reinterpret_cast<const float4*>(t.grad + i);
@@ -213,11 +223,47 @@ __device__ __forceinline__ void adamw_item(const mdemi_tensor_ref& t, const mdem
       const opt_f32x4_t pv = {p.x, p.y, p.z, p.w};
       *reinterpret_cast<opt_bf16x4_t*>(p16 + i) = __builtin_convertvector(pv, opt_bf16x4_t);
     }
+    if constexpr (EMA) {
+      if (ema) {
+        float4 e = evec ? *reinterpret_cast<const float4*>(ema + i)
+                        : make_float4(ema[i], ema[i + 1], ema[i + 2], ema[i + 3]);
+        e.x = fmaf(omd, p.x - e.x, e.x); e.y = fmaf(omd, p.y - e.y, e.y);
+        e.z = fmaf(omd, p.z - e.z, e.z); e.w = fmaf(omd, p.w - e.w, e.w);
+        if (evec) {
+          *reinterpret_cast<float4*>(ema + i) = e;
+        } else {
+          ema[i] = e.x; ema[i + 1] = e.y; ema[i + 2] = e.z; ema[i + 3] = e.w;
+        }
+      }
+    }
   }
   for (int64_t i = vend + threadIdx.x; i < end; i += OPT_THREADS) {
     upd(t.grad[i], t.param[i], t.exp_avg[i], t.exp_avg_sq[i]);
     if (p16) p16[i] = (__bf16)t.param[i];
+    if constexpr (EMA) {
+      if (ema) {
+        const float e = ema[i];
+        ema[i] = fmaf(omd, t.param[i] - e, e);
+      }
+    }
   }
+}
+
+// the averaged weights' arguments (mdemi_adamw_step_ema16 / mdemi_adamw_step_dev_ema16): one
+// pointer per table entry (null: that tensor keeps no average) and the decay of this update,
+// min(decay, (1 + n) / (10 + n)) under warm-up with n = state->updates, which the trailing
+// tick kernel advances after every applied step
+struct EmaArgs {
+  float* const* tab;
+  const mdemi_ema_state* state;
+  float decay;
+  int warmup;
+};
+
+__device__ __forceinline__ float ema_decay_now(const EmaArgs& ea) {
+  if (!ea.warmup) return ea.decay;
+  const float n = (float)ea.state->updates;
+  return fminf(ea.decay, (1.f + n) / (10.f + n));
 }
 
 __device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
@@ -230,13 +276,15 @@ __device__ __forceinline__ float clip_coef(const float* sumsq, float max_norm) {
 // gradients are not finite -- !isfinite(sumsq[0]), the scalar mdemi_grad_sumsq left --
 // returns after that one read and writes nothing.  The unguarded instantiation compiles
 // to the body it had before the template.
-template <bool GUARD>
+// EMA: also keep the averaged weights (adamw_item); `ema` is read by that instantiation only,
+// so <false> / <true> without it compile to the instructions they had before the switch.
+template <bool GUARD, bool EMA = false>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(const mdemi_tensor_ref* __restrict__ tl,
                                                             const int* __restrict__ chunk_tensor,
                                                             const int* __restrict__ chunk_index, AdamGroups groups,
                                                             const float* __restrict__ sumsq, float max_norm, float gs,
                                                             int step, const int* __restrict__ tensor_steps,
-                                                            void* const* __restrict__ p16tab) {
+                                                            void* const* __restrict__ p16tab, EmaArgs ema) {
   if constexpr (GUARD) {
     if (!isfinite(sumsq[0])) return;
   }
@@ -245,13 +293,19 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_kernel(const mdemi_tensor_r
   const mdemi_tensor_ref t = tl[ti];
   const int64_t beg = (int64_t)chunk_index[item] * OPT_CHUNK;
   const int s = tensor_steps ? tensor_steps[t.step_slot] + 1 : step;
-  adamw_item(t, groups.g[t.group], clip_coef(sumsq, max_norm), gs, (float)s, beg, min(t.numel, beg + OPT_CHUNK),
-             p16tab ? (__bf16*)p16tab[ti] : nullptr);
+  if constexpr (EMA) {
+    adamw_item<true>(t, groups.g[t.group], clip_coef(sumsq, max_norm), gs, (float)s, beg,
+                     min(t.numel, beg + OPT_CHUNK), p16tab ? (__bf16*)p16tab[ti] : nullptr, ema.tab[ti],
+                     ema_decay_now(ema));
+  } else {
+    adamw_item(t, groups.g[t.group], clip_coef(sumsq, max_norm), gs, (float)s, beg, min(t.numel, beg + OPT_CHUNK),
+               p16tab ? (__bf16*)p16tab[ti] : nullptr);
+  }
 }
 
 // capturable form: hyperparameters of step s (= *step_dev, steps already taken)
 // from row min(s, nsteps - 1) of a device schedule table
-template <bool GUARD>
+template <bool GUARD, bool EMA = false>
 __global__ __launch_bounds__(OPT_THREADS) void adamw_dev_kernel(const mdemi_tensor_ref* __restrict__ tl,
                                                                 const int* __restrict__ chunk_tensor,
                                                                 const int* __restrict__ chunk_index,
@@ -260,7 +314,8 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_dev_kernel(const mdemi_tens
                                                                 const int* __restrict__ step_dev,
                                                                 const int* __restrict__ tensor_steps,
                                                                 const float* __restrict__ sumsq, float max_norm,
-                                                                float gs, void* const* __restrict__ p16tab) {
+                                                                float gs, void* const* __restrict__ p16tab,
+                                                                EmaArgs ema) {
   if constexpr (GUARD) {
     if (!isfinite(sumsq[0])) return;
   }
@@ -271,16 +326,23 @@ __global__ __launch_bounds__(OPT_THREADS) void adamw_dev_kernel(const mdemi_tens
   const mdemi_adamw_group gp = sched[(int64_t)min(s, nsteps - 1) * ngroups + t.group];
   const int64_t beg = (int64_t)chunk_index[item] * OPT_CHUNK;
   const int bc = tensor_steps ? tensor_steps[t.step_slot] + 1 : s + 1;
-  adamw_item(t, gp, clip_coef(sumsq, max_norm), gs, (float)bc, beg, min(t.numel, beg + OPT_CHUNK),
-             p16tab ? (__bf16*)p16tab[ti] : nullptr);
+  if constexpr (EMA) {
+    adamw_item<true>(t, gp, clip_coef(sumsq, max_norm), gs, (float)bc, beg, min(t.numel, beg + OPT_CHUNK),
+                     p16tab ? (__bf16*)p16tab[ti] : nullptr, ema.tab[ti], ema_decay_now(ema));
+  } else {
+    adamw_item(t, gp, clip_coef(sumsq, max_norm), gs, (float)bc, beg, min(t.numel, beg + OPT_CHUNK),
+               p16tab ? (__bf16*)p16tab[ti] : nullptr);
+  }
 }
 
 // after the update: advance the optimizer's step counter and/or every listed
-// parameter's own counter (torch's state[p]["step"] += 1 for params with a grad)
+// parameter's own counter (torch's state[p]["step"] += 1 for params with a grad);
+// ema (the averaged-weights forms): its update count too
 __global__ __launch_bounds__(256) void step_tick_kernel(int* step_dev, const mdemi_tensor_ref* __restrict__ tl, int nt,
-                                                        int* tensor_steps) {
+                                                        int* tensor_steps, mdemi_ema_state* ema) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (step_dev && i == 0) step_dev[0] += 1;
+  if (ema && i == 0) ema->updates += 1;
   if (tensor_steps && i < nt) tensor_steps[tl[i].step_slot] += 1;
 }
 
@@ -288,17 +350,20 @@ __global__ __launch_bounds__(256) void step_tick_kernel(int* step_dev, const mde
 // advances the per-parameter counters and clears the streak; a skipped one leaves them and is
 // counted.  The schedule position *step_dev (capturable form) advances either way.  One thread
 // owns *step_dev and the guard state; every address is fixed, so a captured graph advances
-// them on every replay.
+// them on every replay.  ema (optional): the averaged weights' update count, advanced by an
+// applied step only.
 __global__ __launch_bounds__(256) void guarded_tick_kernel(int* step_dev, const mdemi_tensor_ref* __restrict__ tl,
                                                            int nt, int* tensor_steps,
                                                            const float* __restrict__ sumsq,
-                                                           mdemi_guard_state* __restrict__ guard) {
+                                                           mdemi_guard_state* __restrict__ guard,
+                                                           mdemi_ema_state* ema) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool ok = isfinite(sumsq[0]);
   if (i == 0) {
     const int at = step_dev ? step_dev[0] : guard->calls;  // 0-based index of this step
     if (ok) {
       guard->consecutive = 0;
+      if (ema) ema->updates += 1;
     } else {
       guard->skipped += 1;
       guard->consecutive += 1;
@@ -460,10 +525,10 @@ extern "C" int mdemi_adamw_step16(const mdemi_tensor_ref* tensors_dev, int32_t n
   const int* ci = ct + nitems;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, g, sumsq,
-                     max_norm, grad_scale, step, (const int*)tensor_steps, param16_dev);
+                     max_norm, grad_scale, step, (const int*)tensor_steps, param16_dev, EmaArgs{});
   if (tensor_steps)
     hipLaunchKernelGGL(step_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)nullptr,
-                       tensors_dev, ntensors, (int*)tensor_steps);
+                       tensors_dev, ntensors, (int*)tensor_steps, (mdemi_ema_state*)nullptr);
   return check_launch("adamw_step");
 }
 
@@ -488,9 +553,9 @@ extern "C" int mdemi_adamw_step_dev16(const mdemi_tensor_ref* tensors_dev, int32
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(adamw_dev_kernel<false>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, sched_dev,
                      nsteps, ngroups, (const int*)step_dev, (const int*)tensor_steps, sumsq, max_norm, grad_scale,
-                     param16_dev);
+                     param16_dev, EmaArgs{});
   hipLaunchKernelGGL(step_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)step_dev,
-                     tensors_dev, ntensors, (int*)tensor_steps);
+                     tensors_dev, ntensors, (int*)tensor_steps, (mdemi_ema_state*)nullptr);
   return check_launch("adamw_step_dev");
 }
 
@@ -525,9 +590,9 @@ extern "C" int mdemi_adamw_step_guarded16(const mdemi_tensor_ref* tensors_dev, i
   const int* ci = ct + nitems;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci, g,
-                     sumsq, max_norm, grad_scale, 0, (const int*)tensor_steps, param16_dev);
+                     sumsq, max_norm, grad_scale, 0, (const int*)tensor_steps, param16_dev, EmaArgs{});
   hipLaunchKernelGGL(guarded_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)nullptr,
-                     tensors_dev, ntensors, (int*)tensor_steps, sumsq, guard_dev);
+                     tensors_dev, ntensors, (int*)tensor_steps, sumsq, guard_dev, (mdemi_ema_state*)nullptr);
   return check_launch("adamw_step_guarded");
 }
 
@@ -546,10 +611,94 @@ extern "C" int mdemi_adamw_step_dev_guarded16(const mdemi_tensor_ref* tensors_de
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(adamw_dev_kernel<true>, dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct, ci,
                      sched_dev, nsteps, ngroups, (const int*)step_dev, (const int*)tensor_steps, sumsq, max_norm,
-                     grad_scale, param16_dev);
+                     grad_scale, param16_dev, EmaArgs{});
   hipLaunchKernelGGL(guarded_tick_kernel, dim3((unsigned)cdiv(ntensors, 256)), dim3(256), 0, st, (int*)step_dev,
-                     tensors_dev, ntensors, (int*)tensor_steps, sumsq, guard_dev);
+                     tensors_dev, ntensors, (int*)tensor_steps, sumsq, guard_dev, (mdemi_ema_state*)nullptr);
   return check_launch("adamw_step_dev_guarded");
+}
+
+// Averaged weights (train.ema_decay): the steps above that also keep e += (1 - d)(p_new - e)
+// for every tensor with an ema_dev entry, in the same sweep; see include/mdemi_ext.h.
+static int ema_args(const char* what, float* const* ema_dev, float ema_decay, const mdemi_ema_state* ema_state_dev) {
+  MDEMI_REQUIRE(ema_dev && ema_state_dev, "%s: bad args (ema_dev and ema_state_dev are required)", what);
+  MDEMI_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "%s: ema_decay %g outside [0, 1)", what, (double)ema_decay);
+  return MDEMI_OK;
+}
+
+extern "C" int mdemi_adamw_step_ema16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                                      const mdemi_adamw_group* groups_host, int32_t ngroups, const float* sumsq,
+                                      float max_norm, float grad_scale, int32_t step, int32_t* tensor_steps,
+                                      int64_t nitems, void* const* param16_dev, float* const* ema_dev,
+                                      float ema_decay, int32_t ema_warmup, mdemi_ema_state* ema_state_dev,
+                                      mdemi_guard_state* guard_dev, void* workspace, void* stream) {
+  int rc = ema_args("adamw_step_ema", ema_dev, ema_decay, ema_state_dev);
+  if (rc != MDEMI_OK) return rc;
+  if (guard_dev) {
+    rc = guarded_args("adamw_step_ema", tensors_dev, ntensors, ngroups, tensor_steps, sumsq, grad_scale, nitems,
+                      guard_dev, workspace);
+    if (rc != MDEMI_OK) return rc;
+  }
+  MDEMI_REQUIRE(tensors_dev && ntensors > 0 && groups_host && ngroups > 0 && ngroups <= 4 &&
+                    (step >= 1 || tensor_steps) && nitems > 0 && nitems <= INT32_MAX && workspace && grad_scale > 0.f,
+                "adamw_step_ema: bad args");
+  AdamGroups g;
+  for (int i = 0; i < ngroups; ++i) g.g[i] = groups_host[i];
+  for (int i = ngroups; i < 4; ++i) g.g[i] = groups_host[0];
+  const int* ct = (const int*)workspace;
+  const int* ci = ct + nitems;
+  hipStream_t st = (hipStream_t)stream;
+  const EmaArgs ea{ema_dev, ema_state_dev, ema_decay, ema_warmup != 0};
+  const dim3 tick((unsigned)cdiv(ntensors, 256));
+  if (guard_dev) {
+    hipLaunchKernelGGL((adamw_kernel<true, true>), dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct,
+                       ci, g, sumsq, max_norm, grad_scale, 0, (const int*)tensor_steps, param16_dev, ea);
+    hipLaunchKernelGGL(guarded_tick_kernel, tick, dim3(256), 0, st, (int*)nullptr, tensors_dev, ntensors,
+                       (int*)tensor_steps, sumsq, guard_dev, ema_state_dev);
+  } else {
+    hipLaunchKernelGGL((adamw_kernel<false, true>), dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev, ct,
+                       ci, g, sumsq, max_norm, grad_scale, step, (const int*)tensor_steps, param16_dev, ea);
+    hipLaunchKernelGGL(step_tick_kernel, tick, dim3(256), 0, st, (int*)nullptr, tensors_dev, ntensors,
+                       (int*)tensor_steps, ema_state_dev);
+  }
+  return check_launch("adamw_step_ema");
+}
+
+extern "C" int mdemi_adamw_step_dev_ema16(const mdemi_tensor_ref* tensors_dev, int32_t ntensors,
+                                          const mdemi_adamw_group* sched_dev, int32_t nsteps, int32_t ngroups,
+                                          int32_t* step_dev, int32_t* tensor_steps, const float* sumsq,
+                                          float max_norm, float grad_scale, int64_t nitems,
+                                          void* const* param16_dev, float* const* ema_dev, float ema_decay,
+                                          int32_t ema_warmup, mdemi_ema_state* ema_state_dev,
+                                          mdemi_guard_state* guard_dev, void* workspace, void* stream) {
+  int rc = ema_args("adamw_step_dev_ema", ema_dev, ema_decay, ema_state_dev);
+  if (rc != MDEMI_OK) return rc;
+  if (guard_dev) {
+    rc = guarded_args("adamw_step_dev_ema", tensors_dev, ntensors, ngroups, tensor_steps, sumsq, grad_scale, nitems,
+                      guard_dev, workspace);
+    if (rc != MDEMI_OK) return rc;
+  }
+  MDEMI_REQUIRE(tensors_dev && ntensors > 0 && sched_dev && nsteps > 0 && ngroups > 0 && ngroups <= 4 && step_dev &&
+                    nitems > 0 && nitems <= INT32_MAX && workspace && grad_scale > 0.f,
+                "adamw_step_dev_ema: bad args");
+  const int* ct = (const int*)workspace;
+  const int* ci = ct + nitems;
+  hipStream_t st = (hipStream_t)stream;
+  const EmaArgs ea{ema_dev, ema_state_dev, ema_decay, ema_warmup != 0};
+  const dim3 tick((unsigned)cdiv(ntensors, 256));
+  if (guard_dev) {
+    hipLaunchKernelGGL((adamw_dev_kernel<true, true>), dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev,
+                       ct, ci, sched_dev, nsteps, ngroups, (const int*)step_dev, (const int*)tensor_steps, sumsq,
+                       max_norm, grad_scale, param16_dev, ea);
+    hipLaunchKernelGGL(guarded_tick_kernel, tick, dim3(256), 0, st, (int*)step_dev, tensors_dev, ntensors,
+                       (int*)tensor_steps, sumsq, guard_dev, ema_state_dev);
+  } else {
+    hipLaunchKernelGGL((adamw_dev_kernel<false, true>), dim3((unsigned)nitems), dim3(OPT_THREADS), 0, st, tensors_dev,
+                       ct, ci, sched_dev, nsteps, ngroups, (const int*)step_dev, (const int*)tensor_steps, sumsq,
+                       max_norm, grad_scale, param16_dev, ea);
+    hipLaunchKernelGGL(step_tick_kernel, tick, dim3(256), 0, st, (int*)step_dev, tensors_dev, ntensors,
+                       (int*)tensor_steps, ema_state_dev);
+  }
+  return check_launch("adamw_step_dev_ema");
 }
 
 // Stochastic depth (timm DropPath, swin_transformer.py:181,243-244):

@@ -113,7 +113,11 @@ class GuardState(ctypes.Structure):  # include/mdemi_ext.h mdemi_guard_state
     _fields_ = [("skipped", i32), ("consecutive", i32), ("last_skipped", i32), ("calls", i32)]
 
 
-AUG_MAX_SPANS = 8  # include/mdemi_ext.h MDEMI_AUG_MAX_SPANS
+class EmaState(ctypes.Structure):  # include/mdemi_ext.h mdemi_ema_state
+    _fields_ = [("updates", i32)]
+
+
+AUG_MAX_SPANS = 8 # include/mdemi_ext.h MDEMI_AUG_MAX_SPANS
 
 
 class AugSample(ctypes.Structure):  # include/mdemi_ext.h mdemi_aug_sample
@@ -251,6 +255,10 @@ _SIGS = {
                                                   vp, vp, vp]),
     "mdemi_adamw_step_dev_guarded16": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, f32, f32, i64, vp, vp, vp,
                                                       vp]),
+    "mdemi_adamw_step_ema16": (ctypes.c_int, [vp, i32, ctypes.POINTER(AdamWGroup), i32, vp, f32, f32, i32, vp, i64, vp,
+                                              vp, f32, i32, vp, vp, vp, vp]),
+    "mdemi_adamw_step_dev_ema16": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, f32, f32, i64, vp, vp, f32, i32,
+                                                  vp, vp, vp, vp]),
 }
 
 _lib = None

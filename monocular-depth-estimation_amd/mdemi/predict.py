@@ -166,10 +166,21 @@ def export_predictions(model, batches: Iterable, out_dir: str, data_type: str, e
     return written
 
 
-def _load_weights(model, filename: str) -> None:
+def require_ema(state, filename: str, who: str) -> None:
+    """Exit with a message unless the checkpoint dict holds averaged weights."""
+    if not isinstance(state, dict) or state.get("ema_state_dict") is None:
+        raise SystemExit(f"{who}: {filename!r} holds no ema_state_dict -- it was not written by a run with "
+                         "train.ema_decay set; drop --ema to use its model_state_dict")
+
+
+def _load_weights(model, filename: str, ema: bool = False) -> None:
+    """ema: the file's averaged weights (ema_state_dict) instead of model_state_dict."""
     from .utils import checkpoint as ck
     state = ck.read_checkpoint(filename)
-    if isinstance(state, dict) and "model_state_dict" in state:  # utils.common_utils.save_checkpoint's file
+    if ema:
+        require_ema(state, filename, "--ema")
+        state = state["ema_state_dict"]
+    elif isinstance(state, dict) and "model_state_dict" in state:  # utils.common_utils.save_checkpoint's file
         state = state["model_state_dict"]
     ck.load_checkpoint(model, state, strict=False)
 
@@ -184,6 +195,8 @@ def main(argv=None) -> List[str]:
     ap.add_argument("--batch-size", type=int, default=None, help="default: the config's eval batch size, else 1")
     ap.add_argument("--list-root", default=None, help="directory of the train_test_inputs file lists")
     ap.add_argument("--graph", action="store_true", help="replay the prediction as a captured hipGraph")
+    ap.add_argument("--ema", action="store_true", help="predict with the checkpoint's averaged weights "
+                                                       "(ema_state_dict, written under train.ema_decay)")
     ap.add_argument("--cmap", default="jet")
     ap.add_argument("--no-colour", action="store_true")
     ap.add_argument("--no-raw16", action="store_true")
@@ -201,7 +214,7 @@ def main(argv=None) -> List[str]:
         raise RuntimeError("mdemi.predict needs a GPU")
     dev = torch.device("cuda", torch.cuda.current_device())
     model = build_model(opt, drop_path=0.0)
-    _load_weights(model, args.checkpoint)
+    _load_weights(model, args.checkpoint, ema=args.ema)
     model.to(dev).eval()
 
     kw = {} if args.list_root is None else {"list_root": args.list_root}

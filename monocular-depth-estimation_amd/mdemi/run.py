@@ -37,6 +37,11 @@ def _args(argv):
     ap.add_argument("--nonfinite", default=None, choices=["stop", "skip"],
                     help="override the config's train.nonfinite: stop at a non-finite step (the default), or "
                          "skip its update on the device and go on")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="override the config's train.ema_decay: keep an exponential moving average of the "
+                         "weights with this decay, validate it and choose best.pth on it")
+    ap.add_argument("--ema", action="store_true",
+                    help="with --test: evaluate the checkpoint's averaged weights (ema_state_dict)")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many optimizer steps (in all)")
     return ap.parse_args(argv)
 
@@ -89,8 +94,15 @@ def main(argv=None) -> int:
     opt = parse(args.opt, write_option=rank == 0 and not args.test)
     if args.nonfinite is not None:
         opt.setdefault("train", {})["nonfinite"] = args.nonfinite
+    if args.ema_decay is not None:
+        opt.setdefault("train", {})["ema_decay"] = args.ema_decay
     from .train.builder import nonfinite_policy
+    from .train.ema import ema_config
     nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
+    ema_config(opt)  # and so does a bad train.ema_decay / ema_warmup / ema_validate
+    if args.ema and not args.test:
+        raise SystemExit("mdemi.run --ema selects the weights --test evaluates; to train with averaged weights set "
+                         "train.ema_decay (or --ema-decay)")
     out_dir = opt["output_dir"]
     data_type = opt["dataset"]["data_type"].upper()
     eval_opt = dict(opt.get("eval", {}))
@@ -101,6 +113,9 @@ def main(argv=None) -> int:
         raise SystemExit("mdemi.run --test: missing checkpoint -- pass --checkpoint FILE or set the config's "
                          "\"checkpoint\" key")
     ck = _read_checkpoint(ck_path) if ck_path else None
+    if args.ema:
+        from .predict import require_ema
+        require_ema(ck, ck_path, "mdemi.run --test --ema")
 
     # 3. both loaders and their workers, before the device is selected: no worker is forked
     #    from a process that has made a HIP call (_loader)
@@ -149,11 +164,13 @@ def main(argv=None) -> int:
         if args.test:
             from .predict import _load_weights
             model = build_model(opt, drop_path=0.0)
-            _load_weights(model, ck_path)
+            _load_weights(model, ck_path, ema=args.ema)
             model.to(dev).eval()
             metrics = {k: float(v) for k, v in evaluate(model, test_batches(), eval_opt, data_type,
                                                         weight_by_count=True).items()}
             rec = {"type": "test", "checkpoint": ck_path, **metrics}
+            if args.ema:
+                rec["weights"] = "ema"
             if rank == 0:
                 os.makedirs(out_dir, exist_ok=True)
                 with open(os.path.join(out_dir, "log.jsonl"), "a", encoding="utf-8") as f:
@@ -177,8 +194,9 @@ def main(argv=None) -> int:
         batches = TrainBatches(train_it, train_ds.transform(), trainer.num_accum, spe, seed=args.seed, rank=rank,
                                start_epoch=start_epoch, start_step=start_step)
 
-        def validate():
-            return evaluate(trainer.model, test_batches(), eval_opt, data_type, weight_by_count=True)
+        def validate(model=None):  # fit names the model when it validates averaged weights
+            return evaluate(model if model is not None else trainer.model, test_batches(), eval_opt, data_type,
+                            weight_by_count=True)
 
         return fit(trainer, batches, validate, opt, out_dir, steps_per_epoch=spe, start_epoch=start_epoch,
                    start_step=start_step, max_steps=args.max_steps, rank=rank, world=world, best=best,

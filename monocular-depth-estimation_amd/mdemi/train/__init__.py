@@ -8,3 +8,4 @@ from .loss import BinsChamferLoss, SILogLoss  # noqa: F401
 from .ddp import GradAllReduce, broadcast_parameters  # noqa: F401
 from .builder import Trainer, TrainLoss, build_from_config  # noqa: F401
 from .telemetry import NonFiniteStep, Telemetry, decode_ring  # noqa: F401
+from .ema import ModelEma  # noqa: F401

@@ -29,6 +29,11 @@ unchanged, onto this framework's objects:
                            AdamW step drops it on the device and the run goes on, until more
                            than train.max_consecutive_skips (default 10) follow one another
                            (a decision; the reference does not pin it)
+  train.ema_decay       -> absent / null: off.  A float in [0, 1): ModelEma (train.ema), an averaged
+                           copy of the weights the AdamW kernel updates in its own sweep; it is
+                           what gets validated and what best.pth is chosen on.  train.ema_warmup
+                           (bool) ramps the decay as min(decay, (1 + n) / (10 + n));
+                           train.ema_validate "ema" (default) or "both" (the raw weights too)
   train.num_accum       -> micro-steps accumulated per optimizer step (DDP no_sync
                            on all but the last)
   train.freeze_encoder_bn / freeze_all_bn -> BatchNorm modules kept in eval mode
@@ -249,9 +254,12 @@ class Trainer:
     masks differ per replay."""
 
     def __init__(self, opt, model, criterion, optimizer, scheduler, ddp=None, precision="fp32", graph=False,
-                 telemetry=None):
+                 telemetry=None, ema=None):
         tr = opt.get("train", {})
         self.opt, self.model, self.criterion = opt, model, criterion
+        # train.ema.ModelEma (or None): the averaged weights; the optimizer already holds their
+        # addresses (FusedAdamW.set_ema), the trainer saves, restores and hands them to fit
+        self.ema = ema
         # train.telemetry.Telemetry (or None): one record per optimizer step, pushed on the
         # step's stream right after the update -- inside the capture in graph mode
         self.telemetry = telemetry
@@ -365,8 +373,13 @@ class Trainer:
     def save(self, prefix, save_dir, current_iter, best_value, best_epoch=None, best_iter=None, model_only=False):
         """common_utils.save_checkpoint of this trainer's model and optimizer at self.epoch."""
         from ..utils.common_utils import save_checkpoint
+        extra = None
+        if self.ema is not None:  # two more keys; the reference's loaders ignore them
+            extra = {"ema_state_dict": self.ema.state_dict(),
+                     "ema_meta": {"decay": self.ema.decay, "warmup": self.ema.warmup,
+                                  "updates": self.optimizer.ema_updates()}}
         save_checkpoint(prefix, self.model, self.optimizer, self.epoch, current_iter, best_value, save_dir,
-                        best_epoch=best_epoch, best_iter=best_iter, model_only=model_only)
+                        best_epoch=best_epoch, best_iter=best_iter, model_only=model_only, extra=extra)
 
     def buffers_finite(self):
         """Whether every floating-point buffer of the model (BatchNorm running statistics) is
@@ -380,11 +393,22 @@ class Trainer:
         """Load a save_checkpoint file (the reference's format): model weights, optimizer
         state (moments and per-parameter step counts), epoch, and the OneCycle position
         = optimizer steps taken.  A captured step is re-captured after the next eager step
-        when the load replaced state tensors (FusedAdamW.layout_version).  Returns the file's
+        when the load replaced state tensors (FusedAdamW.layout_version).  With averaged
+        weights (self.ema) the file's ema_state_dict and update count are restored in place;
+        a file without them restarts the averages from the loaded weights.  Returns the file's
         dict."""
         from ..utils.common_utils import load_checkpoint
         dev = next(self.model.parameters()).device
         ck = load_checkpoint(path, self.model, self.optimizer, map_location=dev)
+        if self.ema is not None:
+            if ck.get("ema_state_dict") is not None:
+                self.ema.load_state_dict(ck["ema_state_dict"])
+                self.optimizer.set_ema_updates(int((ck.get("ema_meta") or {}).get("updates", 0)))
+            else:
+                self.ema.reset(self.model)
+                self.optimizer.set_ema_updates(0)
+                from ..utils.common_utils import dprint
+                dprint(f"{path} holds no ema_state_dict: the averaged weights start from the loaded weights")
         self.epoch = int(ck.get("epoch", 0) or 0)
         if self.scheduler is not None:
             self.scheduler.set_position(self.optimizer.step_count)
@@ -422,6 +446,8 @@ def build_from_config(opt, device=None, world=1, steps_per_epoch=None, ddp_bucke
     graph select the mixed-precision / hipGraph-captured step (Trainer); telemetry
     (train.telemetry.Telemetry) records every step's loss and gradient norm on the device."""
     name = opt["model"]["name"]
+    from .ema import ModelEma, ema_config
+    ema_decay, ema_warmup, _ = ema_config(opt)  # a bad train.ema_* key fails before anything is built
     if device is not None and torch.device(device).type == "meta":
         with torch.device("meta"):
             model = build_model(opt, drop_path)
@@ -438,8 +464,12 @@ def build_from_config(opt, device=None, world=1, steps_per_epoch=None, ddp_bucke
         from .ddp import GradAllReduce, broadcast_parameters
         broadcast_parameters(model)
         grad_ar = GradAllReduce(model, bucket_mb=ddp_bucket_mb)
+    ema = None
+    if ema_decay is not None:  # after the broadcast: every rank's average starts from rank 0's weights
+        ema = ModelEma(opt, model, ema_decay, ema_warmup)
+        optimizer.set_ema(ema.pairs(model), ema_decay, ema_warmup)
     precision = precision or opt.get("train", {}).get("precision", "fp32")
     trainer = Trainer(opt, model, criterion, optimizer, scheduler, grad_ar, precision=precision, graph=graph,
-                      telemetry=telemetry)
+                      telemetry=telemetry, ema=ema)
     trainer.train_mode()
     return trainer

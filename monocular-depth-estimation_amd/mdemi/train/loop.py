@@ -34,6 +34,7 @@ import torch
 from .. import _lib as L
 from ..utils.dist_utils import all_reduce_dict
 from .builder import nonfinite_policy, optimizer_steps_per_epoch
+from .ema import ema_config
 from .telemetry import NonFiniteStep
 
 LOG_NAME = "log.jsonl"
@@ -146,7 +147,11 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
 
     train_batches yields one list of train.num_accum (image, gt) micro-batches per optimizer
     step, starting at (start_epoch, start_step); validate() returns the metric dict
-    (evaluate(..., weight_by_count=True)) and is called on every rank.  telemetry defaults to
+    (evaluate(..., weight_by_count=True)) and is called on every rank.  With averaged weights
+    (trainer.ema, train.ema_decay) it is called as validate(model) instead: on trainer.ema.module
+    after ModelEma.sync_buffers -- the "valid" record then carries "weights": "ema" and best.pth
+    is chosen on its abs_rel -- and, under train.ema_validate "both", on trainer.model too, for
+    a second record with "weights": "model".  telemetry defaults to
     trainer.telemetry.  ``best`` is (abs_rel, epoch, iter) of the best checkpoint so far
     (a resumed run).  Rank 0 writes out_dir/log.jsonl -- {"type": "train", ...} every
     train.print_freq steps, {"type": "valid", ...} per validation -- and latest.pth /
@@ -167,6 +172,11 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     if rank == 0:
         os.makedirs(out_dir, exist_ok=True)
     best_value, best_epoch, best_iter = best if best is not None else (math.inf, None, None)
+
+    # averaged weights (train.ema_decay): validate(model) is then called with the model to
+    # evaluate -- trainer.ema.module, and trainer.model as well under train.ema_validate "both"
+    ema = getattr(trainer, "ema", None)
+    ema_validate = ema_config(opt)[2]
 
     policy, max_skips = nonfinite_policy(opt)
     skip_mode = policy == "skip"
@@ -283,19 +293,33 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
         t0 = time.perf_counter()
         if skip_mode:
             require_finite_model()
-        metrics = {k: float(v) for k, v in validate().items()}
+        raw = None
+        if ema is None:
+            metrics = {k: float(v) for k, v in validate().items()}
+        else:  # the averaged weights under the live model's current buffers
+            ema.sync_buffers(trainer.model)
+            metrics = {k: float(v) for k, v in validate(ema.module).items()}
+            if ema_validate == "both":
+                raw = {k: float(v) for k, v in validate(trainer.model).items()}
         if hasattr(trainer, "train_mode"):
             trainer.train_mode()  # evaluate() restores model.train(); frozen BatchNorms go back to eval
         improved = metrics["abs_rel"] < best_value
         if improved:
             best_value, best_epoch, best_iter = metrics["abs_rel"], epoch, it
         rec = {"type": "valid", "epoch": epoch, "iter": it, "step": done, **metrics, "best": improved}
+        recs = [rec]
+        if ema is not None:
+            rec["weights"] = "ema"
+            if raw is not None:  # for the record only: best.pth is chosen on the averaged weights
+                recs.append({"type": "valid", "epoch": epoch, "iter": it, "step": done, **raw, "best": False,
+                             "weights": "model"})
         if rank == 0:
             trainer.save("latest", out_dir, it, best_value, best_epoch=best_epoch, best_iter=best_iter)
             if improved:
                 trainer.save("best", out_dir, it, best_value, best_epoch=best_epoch, best_iter=best_iter)
-            _append(log_path, rec)
-            log(json.dumps(rec))
+            for r in recs:
+                _append(log_path, r)
+                log(json.dumps(r))
         validated_at = done
         t_window += time.perf_counter() - t0  # validation time is not training throughput
 

@@ -35,7 +35,13 @@ class FusedAdamW:
     no host synchronisation.  ``step_count`` stays the schedule position and advances on every
     step; the per-parameter counts do not advance on a skipped one, so the ``steps`` mirror is
     read back from the device where it is needed (state_dict, skipped_steps) instead of being
-    advanced blindly."""
+    advanced blindly.
+
+    set_ema(...) (train.ema_decay): the step also keeps an exponential moving average of the
+    weights, through mdemi_adamw_step_ema16 / mdemi_adamw_step_dev_ema16 -- the same update
+    with one more read and write per parameter, with the guard when skip_nonfinite (a dropped
+    step leaves the averages alone) and the device schedule when capturable.  Without it no
+    average exists and step() calls the entry points above."""
 
     def __init__(self, param_groups, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=0.0,
                  capturable=False, skip_nonfinite=False):
@@ -87,6 +93,49 @@ class FusedAdamW:
         # for every parameter a bf16 GEMM has read (bf16 storage), so the next forward
         # finds a valid copy instead of casting each weight again
         self._b16 = {}
+        # averaged weights (set_ema): parameter -> fp32 average the update also writes
+        # (mdemi_adamw_step_ema16 / mdemi_adamw_step_dev_ema16); None: no average, and step()
+        # calls the entry points it always did
+        self._ema = None
+        self._ema_decay, self._ema_warmup = 0.0, False
+        self._ema_dev = None  # mdemi_ema_state (updates), advanced on the device
+        self._ema_updates0 = 0  # the count the state starts from (a resumed run)
+        self._tbl_ema = None
+
+    # ---- averaged weights ----
+    def set_ema(self, averages, decay, warmup=False):
+        """Keep an exponential moving average of the weights: ``averages`` maps parameters of
+        this optimizer to fp32 tensors of the same shape, which every applied step moves
+        towards the new weights, e += (1 - d)(p - e), in the sweep that writes them; d is
+        ``decay``, or min(decay, (1 + n) / (10 + n)) after n updates with ``warmup``.  A
+        parameter that is not a key keeps no average.  The pointers ride in the step's device
+        table; the call bumps ``layout_version`` (a captured step re-captures)."""
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"FusedAdamW.set_ema: decay must be in [0, 1), got {decay!r}")
+        for p, e in averages.items():
+            if p not in self._slot:
+                raise ValueError("FusedAdamW.set_ema: a key is not a parameter of this optimizer")
+            if e.dtype != torch.float32 or e.shape != p.shape or not e.is_contiguous():
+                raise ValueError(f"FusedAdamW.set_ema: the average of a {tuple(p.shape)} parameter must be a "
+                                 f"contiguous fp32 tensor of that shape, got {tuple(e.shape)} {e.dtype}")
+        self._ema = dict(averages)
+        self._ema_decay, self._ema_warmup = decay, bool(warmup)
+        self._tbl_key = None
+        self.layout_version += 1
+
+    def ema_updates(self):
+        """Applied steps the averages have taken: one small device-to-host copy (a
+        synchronisation: call it where the telemetry ring is drained, not per step)."""
+        if self._ema is None:
+            raise RuntimeError("FusedAdamW.ema_updates: no averages set (set_ema)")
+        return int(self._ema_dev.item()) if self._ema_dev is not None else int(self._ema_updates0)
+
+    def set_ema_updates(self, n):
+        """Resume: the update count, written in place (a captured step keeps its address)."""
+        self._ema_updates0 = int(n)
+        if self._ema_dev is not None:
+            self._ema_dev.fill_(int(n))
 
     # ---- capturable schedule ----
     def set_schedule(self, rows):
@@ -125,7 +174,7 @@ class FusedAdamW:
         return [p for g in self.param_groups for p in g["params"] if p.grad is not None]
 
     def _refs(self):
-        refs, items_t, items_c, slots, p16 = [], [], [], [], []
+        refs, items_t, items_c, slots, p16, ema = [], [], [], [], [], []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
                 if p.grad is None:
@@ -145,10 +194,14 @@ class FusedAdamW:
                 slots.append(self._slot[p])
                 b16 = self._b16.get(p)
                 p16.append(b16.data_ptr() if b16 is not None else 0)
+                e = self._ema.get(p) if self._ema is not None else None
+                if e is not None and not (e.is_cuda and e.device == p.device):
+                    raise ValueError("FusedAdamW: an average (set_ema) must live on its parameter's device")
+                ema.append(e.data_ptr() if e is not None else 0)
                 nch = max(1, math.ceil(p.numel() / self._chunk))
                 items_t.extend([ti] * nch)
                 items_c.extend(range(nch))
-        return refs, items_t, items_c, slots, p16
+        return refs, items_t, items_c, slots, p16, ema
 
     def _key(self, params):
         """Every address the pointer table holds: a param, its grad, its state."""
@@ -156,9 +209,13 @@ class FusedAdamW:
         for p in params:
             st = self.state.get(p)
             b16 = self._b16.get(p)
-            key.append((p.data_ptr(), p.grad.data_ptr(),
-                        st["exp_avg"].data_ptr() if st else 0, st["exp_avg_sq"].data_ptr() if st else 0,
-                        b16.data_ptr() if b16 is not None else 0))
+            ent = (p.data_ptr(), p.grad.data_ptr(),
+                   st["exp_avg"].data_ptr() if st else 0, st["exp_avg_sq"].data_ptr() if st else 0,
+                   b16.data_ptr() if b16 is not None else 0)
+            if self._ema is not None:
+                e = self._ema.get(p)
+                ent += (e.data_ptr() if e is not None else 0,)
+            key.append(ent)
         return tuple(key)
 
     @torch.no_grad()
@@ -184,21 +241,25 @@ class FusedAdamW:
             # inside a capture (gradients handed out by the captured backward) the upload is a
             # memcpy node from the pinned host table, which stays alive with the device copy:
             # every replay re-copies the same addresses
-            refs, items_t, items_c, slots, p16 = self._refs()
+            refs, items_t, items_c, slots, p16, ema = self._refs()
             nt, ni = len(refs), len(items_t)
             raw = (L.TensorRef * nt)(*refs)
             rb = (ctypes.sizeof(raw) + 255) // 256 * 256
             pb = (8 * nt + 255) // 256 * 256 if any(p16) else 0  # bf16 copy pointers (mdemi_adamw_step16)
+            eb = (8 * nt + 255) // 256 * 256 if self._ema is not None else 0  # the averages' pointers
             wsb = lib.mdemi_grad_norm_workspace_size(ni)
-            host = torch.empty(rb + pb + wsb, dtype=torch.uint8, pin_memory=True)
+            host = torch.empty(rb + pb + eb + wsb, dtype=torch.uint8, pin_memory=True)
             ctypes.memmove(host.data_ptr(), ctypes.addressof(raw), ctypes.sizeof(raw))
             if pb:
                 host[rb:rb + 8 * nt].view(torch.int64).copy_(torch.tensor(p16, dtype=torch.int64))
-            w0 = rb + pb
+            if eb:
+                host[rb + pb:rb + pb + 8 * nt].view(torch.int64).copy_(torch.tensor(ema, dtype=torch.int64))
+            w0 = rb + pb + eb
             host[w0:w0 + 8 * ni].view(torch.int32).copy_(torch.tensor(items_t + items_c, dtype=torch.int32))
             dev_buf = host.to(dev, non_blocking=True)
             self._tbl = (host, dev_buf, dev_buf.data_ptr(), dev_buf.data_ptr() + w0, nt, ni,
                          dev_buf.data_ptr() + rb if pb else None)
+            self._tbl_ema = dev_buf.data_ptr() + rb + pb if eb else None
             self._tbl_key = self._key(params)
             self._tbl_slots = slots
             self.layout_version += 1
@@ -211,6 +272,10 @@ class FusedAdamW:
             if capturing:
                 raise RuntimeError("FusedAdamW: the guard state must exist before hipGraph capture")
             self._guard_dev = torch.tensor([0, 0, -1, 0], dtype=torch.int32).to(dev)
+        if self._ema is not None and self._ema_dev is None:
+            if capturing:
+                raise RuntimeError("FusedAdamW: the EMA state must exist before hipGraph capture")
+            self._ema_dev = torch.tensor([self._ema_updates0], dtype=torch.int32).to(dev)
         if self._sumsq is None:
             self._sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
         gs = float(self.grad_scale)
@@ -218,7 +283,22 @@ class FusedAdamW:
             L.check(lib.mdemi_grad_sumsq(tl_ptr, nt, ni, gs, self._sumsq.data_ptr(), ws_ptr, L.stream()), "grad_sumsq")
         clip = self._sumsq.data_ptr() if self.max_grad_norm > 0 else None
         steps_ptr = self._steps_dev.data_ptr()
-        if self.skip_nonfinite:
+        if self._ema is not None:
+            # the same update with the averages in its sweep; guard_dev selects the guarded form
+            guard = self._guard_dev.data_ptr() if self.skip_nonfinite else None
+            sumsq = self._sumsq.data_ptr() if self.skip_nonfinite else clip
+            ema = (self._tbl_ema, self._ema_decay, int(self._ema_warmup), self._ema_dev.data_ptr(), guard)
+            if self.capturable:
+                sched, nsteps = self._device_schedule(dev, self.step_count)
+                L.check(lib.mdemi_adamw_step_dev_ema16(tl_ptr, nt, sched.data_ptr(), nsteps, len(self.param_groups),
+                                                       self._step_dev.data_ptr(), steps_ptr, sumsq, self.max_grad_norm,
+                                                       gs, ni, p16_ptr, *ema, ws_ptr, L.stream()),
+                        "adamw_step_dev_ema")
+            else:
+                L.check(lib.mdemi_adamw_step_ema16(tl_ptr, nt, self._host_groups(), len(self.param_groups), sumsq,
+                                                   self.max_grad_norm, gs, self.step_count + 1, steps_ptr, ni, p16_ptr,
+                                                   *ema, ws_ptr, L.stream()), "adamw_step_ema")
+        elif self.skip_nonfinite:
             sumsq, guard = self._sumsq.data_ptr(), self._guard_dev.data_ptr()
             if self.capturable:
                 sched, nsteps = self._device_schedule(dev, self.step_count)
@@ -288,6 +368,11 @@ class FusedAdamW:
         Under skip_nonfinite only the schedule position advances here: whether the
         per-parameter counts moved was decided on the device (_refresh_steps)."""
         self.step_count += 1
+        if self._ema is not None:
+            # the averages moved through raw pointers and, as frozen tensors, are outside the
+            # weight epoch: a bf16 copy an evaluation recorded on one is stale from here on
+            for e in self._ema.values():
+                e.__dict__.pop("_mdemi_b16", None)
         if self.skip_nonfinite:
             return
         for s in self._tbl_slots:

@@ -26,13 +26,19 @@ def _unwrap(model):
 
 
 def save_checkpoint(prefix: str, model, optimizer, current_epoch, current_iter, best_value, save_dir: str,
-                    best_epoch=None, best_iter=None, *, model_only: bool = False) -> None:
+                    best_epoch=None, best_iter=None, *, model_only: bool = False, extra=None) -> None:
     """common_utils.py:12-31: ``{save_dir}/{prefix}.pth`` holding epoch, iter, best_epoch /
     best_iter (default: the current ones), the model's state_dict, the optimizer's
     state_dict (None with model_only) and best.  FusedAdamW.state_dict() is torch.optim.AdamW's
     layout (per-parameter "step", params index lists), so the file loads into the reference's
-    torch AdamW and back."""
+    torch AdamW and back.  ``extra``: further top-level keys (the averaged weights'
+    ema_state_dict / ema_meta); none may shadow a key above, and a loader that does not know
+    them ignores them."""
     model = _unwrap(model)
+    extra = dict(extra or {})
+    clash = sorted(set(extra) & set(CHECKPOINT_KEYS))
+    if clash:
+        raise ValueError(f"save_checkpoint: extra keys {clash} shadow the checkpoint's own")
     torch.save({
         "epoch": current_epoch,
         "iter": current_iter,
@@ -41,6 +47,7 @@ def save_checkpoint(prefix: str, model, optimizer, current_epoch, current_iter, 
         "model_state_dict": model.state_dict(),
         "optimizer_state_dict": optimizer.state_dict() if not model_only else None,
         "best": best_value,
+        **extra,
     }, f"{save_dir}/{prefix}.pth")
 
 

@@ -1,13 +1,17 @@
-"""Cost of the guarded AdamW step (train.nonfinite: "skip") over the NeW-CRFs-L parameter table.
+"""Cost of the guarded AdamW step (train.nonfinite: "skip") and of the step that keeps averaged
+weights (train.ema_decay) over the NeW-CRFs-L parameter table.
 
 Times, with HIP events around single calls, the update entry points of csrc/misc.hip on
 synthetic tensors of the model's parameter shapes (270 M elements): the unguarded step, the
 guarded step with finite gradients, the guarded step that skips, and mdemi_grad_sumsq alone
-(what "skip" adds per step when the clip is off and nothing else needs the scalar).  The
+(what "skip" adds per step when the clip is off and nothing else needs the scalar), and the
+steps with an average for every tensor (mdemi_adamw_step_ema16 / mdemi_adamw_step_dev_ema16,
+unguarded and guarded): one more 4-B read and write per parameter, 36 B against 28 (38 against
+30 with --b16, which gives every tensor a maintained bf16 copy in all variants).  The
 variants alternate inside every round, after a warm-up; the median over the rounds is reported
 with the 10th / 90th percentile, one JSON line per variant and one with the ratios.
 
-    python tools/guard_bench.py [--version large07] [--rounds 100] [--warmup 10]
+    python tools/guard_bench.py [--version large07] [--rounds 100] [--warmup 10] [--b16]
 """
 import argparse
 import json
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--version", default="large07")
     ap.add_argument("--rounds", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--b16", action="store_true", help="every tensor also has a bf16 copy the update writes")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("guard_bench: needs a GPU")
@@ -56,6 +61,12 @@ def main():
     ws = torch.zeros(lib.mdemi_grad_norm_workspace_size(ni) // 4, dtype=torch.int32)
     ws[:2 * ni] = torch.tensor(items_t + items_c, dtype=torch.int32)
     ws = ws.to(dev)
+    ema = [t.clone() for t in p]
+    ematab = torch.tensor([t.data_ptr() for t in ema], dtype=torch.int64).to(dev)
+    ema_state = torch.zeros(1, dtype=torch.int32, device=dev)
+    p16 = [t.to(torch.bfloat16) for t in p] if args.b16 else None
+    p16tab = torch.tensor([t.data_ptr() for t in p16], dtype=torch.int64).to(dev) if args.b16 else None
+    b16 = p16tab.data_ptr() if args.b16 else None
     tsteps = torch.zeros(nt, dtype=torch.int32, device=dev)
     step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
     guard = torch.tensor([0, 0, -1, 0], dtype=torch.int32).to(dev)
@@ -72,17 +83,28 @@ def main():
     def host(guarded, sq):
         if guarded:
             return lib.mdemi_adamw_step_guarded16(tl, nt, groups, 1, sq.data_ptr(), max_norm, 1.0, tsteps.data_ptr(),
-                                                  ni, None, guard.data_ptr(), wsp, st)
+                                                  ni, b16, guard.data_ptr(), wsp, st)
         return lib.mdemi_adamw_step16(tl, nt, groups, 1, sq.data_ptr(), max_norm, 1.0, 1, tsteps.data_ptr(), ni,
-                                      None, wsp, st)
+                                      b16, wsp, st)
 
     def devf(guarded, sq):
         if guarded:
             return lib.mdemi_adamw_step_dev_guarded16(tl, nt, sched.data_ptr(), 1, 1, step_dev.data_ptr(),
-                                                      tsteps.data_ptr(), sq.data_ptr(), max_norm, 1.0, ni, None,
+                                                      tsteps.data_ptr(), sq.data_ptr(), max_norm, 1.0, ni, b16,
                                                       guard.data_ptr(), wsp, st)
         return lib.mdemi_adamw_step_dev16(tl, nt, sched.data_ptr(), 1, 1, step_dev.data_ptr(), tsteps.data_ptr(),
-                                          sq.data_ptr(), max_norm, 1.0, ni, None, wsp, st)
+                                          sq.data_ptr(), max_norm, 1.0, ni, b16, wsp, st)
+
+    def ema_tail(guarded):
+        return (ematab.data_ptr(), 0.999, 0, ema_state.data_ptr(), guard.data_ptr() if guarded else None, wsp, st)
+
+    def ema_host(guarded, sq):
+        return lib.mdemi_adamw_step_ema16(tl, nt, groups, 1, sq.data_ptr(), max_norm, 1.0, 1, tsteps.data_ptr(), ni,
+                                          b16, *ema_tail(guarded))
+
+    def ema_dev(guarded, sq):
+        return lib.mdemi_adamw_step_dev_ema16(tl, nt, sched.data_ptr(), 1, 1, step_dev.data_ptr(), tsteps.data_ptr(),
+                                              sq.data_ptr(), max_norm, 1.0, ni, b16, *ema_tail(guarded))
 
     variants = {
         "unguarded_host": lambda: host(False, sq_ok),
@@ -91,6 +113,11 @@ def main():
         "unguarded_dev": lambda: devf(False, sq_ok),
         "guarded_dev": lambda: devf(True, sq_ok),
         "guarded_dev_skipped": lambda: devf(True, sq_bad),
+        "ema_host": lambda: ema_host(False, sq_ok),
+        "ema_guarded_host": lambda: ema_host(True, sq_ok),
+        "ema_dev": lambda: ema_dev(False, sq_ok),
+        "ema_guarded_dev": lambda: ema_dev(True, sq_ok),
+        "ema_guarded_dev_skipped": lambda: ema_dev(True, sq_bad),
         "grad_sumsq": lambda: lib.mdemi_grad_sumsq(tl, nt, ni, 1.0, sq_scratch.data_ptr(), wsp, st),
     }
     times = {k: [] for k in variants}
@@ -110,7 +137,12 @@ def main():
         med[name] = statistics.median(ts)
         print(json.dumps({"variant": name, "median_us": round(med[name], 2), "p10_us": round(ts[len(ts) // 10], 2),
                           "p90_us": round(ts[len(ts) * 9 // 10], 2), "rounds": len(ts)}))
-    print(json.dumps({"model": args.version, "elements": sum(shapes), "tensors": nt, "items": ni,
+    print(json.dumps({"model": args.version, "elements": sum(shapes), "tensors": nt, "items": ni, "b16": args.b16,
+                      "ema_over_plain_host": round(med["ema_host"] / med["unguarded_host"], 4),
+                      "ema_over_plain_dev": round(med["ema_dev"] / med["unguarded_dev"], 4),
+                      "ema_guarded_over_guarded_host": round(med["ema_guarded_host"] / med["guarded_host"], 4),
+                      "ema_guarded_over_guarded_dev": round(med["ema_guarded_dev"] / med["guarded_dev"], 4),
+                      "ema_traffic_ratio": round(38 / 30 if args.b16 else 36 / 28, 4),
                       "guarded_over_unguarded_host": round(med["guarded_host"] / med["unguarded_host"], 4),
                       "guarded_over_unguarded_dev": round(med["guarded_dev"] / med["unguarded_dev"], 4),
                       "skipped_over_unguarded_host": round(med["guarded_host_skipped"] / med["unguarded_host"], 4),

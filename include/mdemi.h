@@ -122,6 +122,29 @@ typedef struct mdemi_gemm_desc {
                                       keep/(1-p) scale of a residual branch
                                       (swin_transformer.py:232,239) fused into the proj /
                                       fc2 epilogue.  Batch 1. */
+  /* Optional liveness masks: permission to skip work whose result the caller does not
+   * need (the samples timm DropPath dropped, swin_transformer.py:232,239).  Index i of the
+   * masked dimension belongs to group i / X_live_group; a group whose float entry == 0.0f is
+   * dead (the same [B] tensor as row_scale may be passed).  Read on the device only.  Both
+   * need batch 1, no MDEMI_L_CONV operand and 0 < group < 2^31.  A kernel family may ignore
+   * them: mdemi_gemm_f32 honours both, the 16-bit families (mdemi_gemm_bf16, _f32e, _bf16x)
+   * ignore both and compute every value.
+   *  m_live (rows i of C): the caller does not care which of two values a dead row of C,
+   *    preact and c16 holds: the true one, or what the unchanged epilogue makes of a zero
+   *    accumulator.  A block tile (of the running variant's own height) whose rows are all
+   *    dead runs over zero K tiles; everything after the K loop is unchanged (split
+   *    hand-off, counters, bias, activation, row_scale, residual, stores).  With
+   *    row_scale == m_live and a residual, such rows come out as the residual.
+   *  k_live (reduction index k): the caller asserts that every product over a dead k is
+   *    exactly zero because one operand is all zeros there (with rowsum_a: operand A).  A
+   *    32-element K chunk [32c, 32c + 32) whose k are all dead is skipped whole: no loads,
+   *    no MFMAs, no rowsum_a adds.  Chunks are the family's fixed split granularity, so
+   *    every variant skips the same products and the results are equal as numbers to the
+   *    unmasked call on finite operands.  A split-K piece with no live chunk still writes its
+   *    zero slab and takes part in the combine.
+   * Workspace size, split plan and the autotuned variant do not depend on the masks. */
+  const float* m_live; int64_t m_live_group;
+  const float* k_live; int64_t k_live_group;
 } mdemi_gemm_desc;
 
 size_t mdemi_gemm_workspace_size(const mdemi_gemm_desc* d);
@@ -276,6 +299,13 @@ typedef struct mdemi_winattn_desc {
   float* d_rpb_table;              /* [(2w-1)^2][heads], overwritten */
   float* dq_pad; float* dk_pad; float* dv_pad;   /* [C] sums over pad tokens, overwritten (may be NULL) */
   void* workspace; int64_t workspace_bytes;
+  const float* sample_live;        /* optional [B], read on the device only: a sample whose entry
+                                      == 0.0f is dead (DropPath dropped its branch).  The forward
+                                      writes zeros to a dead sample's out rows and lse; the
+                                      backward, given the same mask, reads none of its tensors,
+                                      writes zeros to its dq / dk / dv rows and adds nothing to
+                                      d_rpb_table or the pad sums -- what the unmasked call
+                                      computes from a zero dout.  Every output is still written. */
 } mdemi_winattn_desc;
 
 size_t mdemi_winattn_fwd_workspace_size(const mdemi_winattn_desc* d);

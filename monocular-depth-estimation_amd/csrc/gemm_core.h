@@ -29,16 +29,6 @@ constexpr int GBM = 128, GBN = 128, GTHREADS = 256;
 constexpr int PMN = GBM + 4;   // [k][row] image pitch (floats)
 template <int BK> struct PitchK { static constexpr int v = BK + 4; };  // [row][k] image pitch
 
-struct FastDiv {
-  uint32_t mul, shift;
-};
-static inline FastDiv make_fastdiv(uint32_t d) {
-  uint32_t c = 0;
-  while ((1u << c) < d) ++c;
-  const uint32_t L = 31 + c;
-  return FastDiv{(uint32_t)(((uint64_t)1 << L) / d + 1), L};
-}
-
 struct GemmParams {
   int M, N, K, batch, split, ktile_per_split;
   const float* A; int64_t lda, a_bs;
@@ -62,7 +52,29 @@ struct GemmParams {
   int* tile_cnt;  // non-null: the last-arriving split of a tile combines the slabs (no reduce launch)
   float* rowsum_out;  // with tile_cnt and split row-sum partials: the last arriver writes the sums here
   void* c16;  // optional bf16 copy (RNE) of the final output, C's layout: the bf16 operand of a later GEMM
+  // optional liveness masks (mdemi_gemm_desc.m_live / k_live; predicates in gemm_plan.h):
+  // honoured by the fp32 family, ignored by the 16-bit families
+  const float* m_live; FastDiv fd_mlive;  // index -> group by multiply-shift
+  const float* k_live; FastDiv fd_klive;
 };
+
+// The block tile of rows [bm, bm + BMT) holds no live row (m_live): it runs over no K tile.
+template <int BMT>
+__device__ __forceinline__ bool tile_rows_dead(const GemmParams& p, int bm) {
+  return p.m_live && range_all_dead(p.m_live, p.fd_mlive, bm, min(bm + BMT, p.M));
+}
+// The first K tile (of depth BK) in [kt, kt_end) that lies in a live 32-element chunk, or a
+// value >= kt_end when there is none (k_live).  Wave-uniform; one chunk test per tile looked
+// at, and a dead chunk is stepped over whole, so BK 16 and BK 32 skip the same products.
+template <int BK>
+__device__ __forceinline__ int live_ktile(const GemmParams& p, int kt, int kt_end) {
+  constexpr int TPC = 32 / BK;  // K tiles per chunk
+  if (p.k_live) {
+    while (kt < kt_end && !chunk_live(p.k_live, p.fd_klive, kt / TPC, p.K)) kt = (kt / TPC + 1) * TPC;
+    kt = __builtin_amdgcn_readfirstlane(kt);  // a scalar register, whatever the mask loads were
+  }
+  return kt;
+}
 
 // One thread's 4 bias-gradient row sums (rows i..i+3) of a K piece: plain stores, or
 // write-through (sc1) stores when the pieces are split (the tile's last arriver may read
@@ -108,11 +120,6 @@ __device__ __forceinline__ float buf_ld1(__amdgpu_buffer_rsrc_t r, int off) {
 // sc1 load (bypasses this CU's L1): reads bytes another workgroup stored sc1 in this launch
 __device__ __forceinline__ float buf_ld1_sc1(__amdgpu_buffer_rsrc_t r, int off) {
   return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 16));
-}
-
-// n / d for 0 <= n < 2^31 by multiply-shift (host-computed magic, exact).
-__device__ __forceinline__ int fdiv(int n, const FastDiv& f) {
-  return (int)(((uint64_t)(uint32_t)n * f.mul) >> f.shift);
 }
 
 template <int OP>

@@ -155,6 +155,15 @@ static int validate(const mdemi_gemm_desc* d) {
   if (d->row_scale)
     MDEMI_REQUIRE(d->batch == 1 && d->row_scale_group > 0 && d->row_scale_group < ((int64_t)1 << 31),
                   "gemm: row_scale needs batch 1 and 0 < row_scale_group < 2^31");
+  if (d->m_live || d->k_live)
+    MDEMI_REQUIRE(d->batch == 1 && d->a_layout != MDEMI_L_CONV && d->b_layout != MDEMI_L_CONV,
+                  "gemm: m_live / k_live need batch 1 and no conv operand");
+  if (d->m_live)
+    MDEMI_REQUIRE(d->m_live_group > 0 && d->m_live_group < ((int64_t)1 << 31) && !d->rowsum_a,
+                  "gemm: m_live needs 0 < m_live_group < 2^31 and no rowsum_a");
+  if (d->k_live)
+    MDEMI_REQUIRE(d->k_live_group > 0 && d->k_live_group < ((int64_t)1 << 31),
+                  "gemm: k_live needs 0 < k_live_group < 2^31");
   if (d->batch_inner > 1)
     MDEMI_REQUIRE(d->batch % d->batch_inner == 0 && !d->aux && !d->residual && !d->preact && !d->rowsum_a,
                   "gemm: batch_inner needs batch %% batch_inner == 0 and no aux/residual/preact/rowsum_a");
@@ -195,6 +204,9 @@ static void fill_params(const mdemi_gemm_desc* d, const GemmPlan& pl, GemmParams
   p.rowsum = d->rowsum_a;
   p.rowscale = d->row_scale;
   if (d->row_scale) p.fd_rs = make_fastdiv((uint32_t)d->row_scale_group);
+  p.m_live = d->m_live; p.k_live = d->k_live;
+  if (d->m_live) p.fd_mlive = make_fastdiv((uint32_t)d->m_live_group);
+  if (d->k_live) p.fd_klive = make_fastdiv((uint32_t)d->k_live_group);
   p.binner = d->batch_inner > 1 ? d->batch_inner : 1;
   p.a_bs2 = p.binner > 1 ? d->a_bstride_inner : 0;
   p.b_bs2 = p.binner > 1 ? d->b_bstride_inner : 0;
@@ -239,9 +251,15 @@ static int* tile_counters(int64_t n, hipStream_t st) {
 }
 // The plan under the process's options; the device is asked for its CU count only where
 // the tail split can apply.
+// A launch that honours a liveness mask takes the plain raster.  The grouped raster hands each
+// XCD one contiguous range of row tiles (or of K pieces) -- with 8 samples on 8 XCDs, about one
+// sample each -- so a dead sample would idle one XCD while the other seven took as long as
+// before (measured: no gain, profiles/drop_skip/).  In the plain raster neighbouring jobs go
+// to different XCDs and the dead ones spread evenly.  The raster never changes a value.
 static GemmPlan plan_for(const mdemi_gemm_desc* d, int mode, int variant) {
   const bool tail = g_opt.tail_split && tail_split_shape(d);
-  return plan_gemm(d, mode, variant, tail ? device_cus() : 0, GemmOptions{tail, g_opt.group_m});
+  const bool masked = mode == GEMM_F32 && (d->m_live || d->k_live);
+  return plan_gemm(d, mode, variant, tail ? device_cus() : 0, GemmOptions{tail, masked ? 0 : g_opt.group_m});
 }
 // workspace of a split plan: slabs, row-sum partials, then the deep combine's column-sum scratch
 static size_t plan_bytes(const mdemi_gemm_desc* d, const GemmPlan& g) {
@@ -337,9 +355,14 @@ static bool tunable(const mdemi_gemm_desc* d, hipStream_t st) {
   return true;
 }
 
-static int choose_variant(const mdemi_gemm_desc* d, hipStream_t st, int mode, const B16Ext* ext = nullptr) {
+static int choose_variant(const mdemi_gemm_desc* d_in, hipStream_t st, int mode, const B16Ext* ext = nullptr) {
   const int forced = mode == GEMM_F32 ? g_variant : mode == GEMM_B16 ? g_variant_b16 : g_variant_m16;
   if (forced >= 0) return forced;
+  // the candidates are timed on the whole product (no liveness mask), so the cached winner of
+  // a shape does not depend on which samples one call happened to drop
+  mdemi_gemm_desc whole = *d_in;
+  whole.m_live = whole.k_live = nullptr;
+  const mdemi_gemm_desc* d = &whole;
   const TuneKey key{d->a_layout, d->b_layout, d->a_op, d->b_op, d->M, d->N, d->K, d->batch, d->split_k, mode};
   {
     std::lock_guard<std::mutex> lk(g_tune_mu);

@@ -46,7 +46,9 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
 
   const int ktiles_total = (p.K + BK - 1) / BK;
   const int kt_begin = job.split ? sidx * p.ktile_per_split : 0;
-  const int kt_end = job.split ? min(ktiles_total, kt_begin + p.ktile_per_split) : ktiles_total;
+  int kt_end = job.split ? min(ktiles_total, kt_begin + p.ktile_per_split) : ktiles_total;
+  if (tile_rows_dead<BMT>(p, bm)) kt_end = kt_begin;  // nothing but the epilogue, on a zero accumulator
+  kt_end = __builtin_amdgcn_readfirstlane(kt_end);
 
   floatx16 acc[IM][2];
 #pragma unroll
@@ -104,21 +106,27 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
     acc_rsum();
   };
 
-  if (PREF && kt_begin < kt_end) {
-    load(kt_begin);
+  // the live K tiles only (k_live; every tile without it): a skipped tile is neither loaded
+  // nor staged, so it adds nothing to the row sums either
+  const int kt_first = live_ktile<BK>(p, kt_begin, kt_end);
+  if (PREF && kt_first < kt_end) {
+    load(kt_first);
     stage(smem);
     __syncthreads();
   }
 
   int cur = 0;
-  for (int kt = kt_begin; kt < kt_end; ++kt) {
-    const bool more = kt + 1 < kt_end;
+  // nk: the live tile after kt, looked up at the end of the tile before (after its barrier,
+  // where nothing but the accumulators is live)
+  int nk = live_ktile<BK>(p, kt_first + 1, kt_end);
+  for (int kt = kt_first; kt < kt_end; kt = nk, nk = live_ktile<BK>(p, kt + 1, kt_end)) {
+    const bool more = nk < kt_end;
     if (!PREF) {  // plain: load, stage, barrier, compute (other workgroups overlap)
       load(kt);
       stage(smem);
       __syncthreads();
-    } else if (more) {  // issue next tile's global loads early; they land under the MFMAs
-      load(kt + 1);
+    } else if (more) {  // issue the next live tile's global loads early; they land under the MFMAs
+      load(nk);
     }
     const float* a_s = smem + cur * (FAT + FB) + aimg * FA;
     const float* b_s = smem + cur * (FAT + FB) + FAT;

@@ -182,7 +182,8 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
 
   const int ktiles_total = (p.K + BK - 1) / BK;
   const int kt_begin = job.split ? sidx * p.ktile_per_split : 0;
-  const int kt_end = job.split ? min(ktiles_total, kt_begin + p.ktile_per_split) : ktiles_total;
+  int kt_end = job.split ? min(ktiles_total, kt_begin + p.ktile_per_split) : ktiles_total;
+  if (tile_rows_dead<BMT>(p, bm)) kt_end = kt_begin;  // nothing but the epilogue, on a zero accumulator
 
   floatx16 acc[IM][IN];
 #pragma unroll
@@ -223,14 +224,14 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
     }
   };
 
-  // One K tile: issue the DMA of tile kt+1 into `nxt`, then the row sums and MFMAs of tile
-  // kt from `cur`.  The two stages are separate __shared__ objects and every call below
-  // names them at compile time (the loop is unrolled by two), so the compiler's LDS alias
+  // One K tile: issue the DMA of the next live tile `nk` into `nxt`, then the row sums and
+  // MFMAs of the tile staged in `cur`.  The two stages are separate __shared__ objects and
+  // every call below names them at compile time (the loop is unrolled by two), so the LDS alias
   // scopes tell it a fragment read of one stage cannot depend on the DMA in flight into the
   // other: without that it waits vmcnt(0) before the first ds_read of every tile and the
   // load no longer overlaps the MFMAs.
-  auto tile = [&](int kt, const float* cur, float* nxt) {
-    if (kt + 1 < kt_end) issue(kt + 1, nxt);
+  auto tile = [&](const float* cur, float* nxt, int nk) {
+    if (nk < kt_end) issue(nk, nxt);
     if (CAN_RSUM && do_rsum) {
 #pragma unroll
       for (int a = 0; a < NA; ++a)
@@ -266,17 +267,21 @@ __global__ __launch_bounds__(GTHREADS) __attribute__((amdgpu_waves_per_eu(OCC, 8
       MDEMI_GSTEP(x) MDEMI_GSTEP(y) MDEMI_GSTEP(z) MDEMI_GSTEP(w)
 #undef MDEMI_GSTEP
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of tile kt+1 has landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of tile nk has landed
     __syncthreads();                                   // ... every wave's, and `cur` is no longer read
   };
 
-  if (kt_begin < kt_end) issue(kt_begin, smem);
+  // the live K tiles only (k_live; every tile without it), each prefetching the next live one
+  int kt = live_ktile<BK>(p, kt_begin, kt_end);
+  if (kt < kt_end) issue(kt, smem);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  for (int kt = kt_begin; kt < kt_end; kt += 2) {
-    tile(kt, smem, smem1);
-    if (kt + 1 >= kt_end) break;
-    tile(kt + 1, smem1, smem);
+  while (kt < kt_end) {
+    const int nk = live_ktile<BK>(p, kt + 1, kt_end);
+    tile(smem, smem1, nk);
+    if (nk >= kt_end) break;
+    kt = live_ktile<BK>(p, nk + 1, kt_end);
+    tile(smem1, smem, kt);
   }
   if (CAN_RSUM && do_rsum) {  // the 8 k-row groups (t >> 5) of each A image, in order
     float4* red = reinterpret_cast<float4*>(smem);

@@ -191,6 +191,37 @@ inline GemmPlan plan_gemm(const mdemi_gemm_desc* d, int mode, int variant, int c
   return g;
 }
 
+// n / d for 0 <= n < 2^31 and 0 < d < 2^31 by multiply-shift: the magic is computed on the
+// host, the division is exact.
+struct FastDiv {
+  uint32_t mul, shift;
+};
+inline FastDiv make_fastdiv(uint32_t d) {
+  uint32_t c = 0;
+  while ((1u << c) < d) ++c;
+  const uint32_t L = 31 + c;
+  return FastDiv{(uint32_t)(((uint64_t)1 << L) / d + 1), L};
+}
+MDEMI_HD int fdiv(int n, const FastDiv& f) { return (int)(((uint64_t)(uint32_t)n * f.mul) >> f.shift); }
+
+// Liveness masks (mdemi_gemm_desc.m_live / k_live): index i belongs to group i / group, and a
+// group whose mask entry == 0.0f is dead (a NaN entry is live).  The kernels ask these two
+// questions with wave-uniform arguments, so each is a scalar decision: a block tile of rows
+// that are all dead runs over no K tile, and a 32-element K chunk (the family's split
+// granularity, aligned from k = 0) with no live k is not loaded.
+// The group size is carried as its multiply-shift reciprocal (make_fastdiv(group)).
+// every index of [i0, i1), 0 <= i0 < i1, is dead
+MDEMI_HD bool range_all_dead(const float* live, const FastDiv& group, int i0, int i1) {
+  for (int g = fdiv(i0, group), last = fdiv(i1 - 1, group); g <= last; ++g)
+    if (live[g] != 0.f) return false;
+  return true;
+}
+// K chunk `chunk` (k in [32 chunk, min(32 chunk + 32, K)), 32 chunk < K) holds a live k
+MDEMI_HD bool chunk_live(const float* live, const FastDiv& group, int chunk, int K) {
+  const int k0 = 32 * chunk;
+  return !range_all_dead(live, group, k0, K - k0 < 32 ? K : k0 + 32);
+}
+
 // XCD-aware linear order: workgroup ids b, b+8, ... (one XCD) take one contiguous range
 // of [0, n), so neighbouring jobs share that XCD's L2.
 MDEMI_HD int xcd_lin(int bid, int n) {

@@ -100,6 +100,7 @@ struct WinParams {
   float* dv; int64_t dv_ld;
   float* partial;  // [nwin][heads][T + 2*HD]: bias-table gradient, pad-key k / v gradient sums
   int off32;       // every row * ld of the backward's column operands fits a 24x24 -> 32-bit multiply
+  const float* live;  // optional [B]: == 0.0f marks a dead sample (mdemi_winattn_desc.sample_live)
 };
 
 // ---------------------------------------------------------------------------
@@ -211,6 +212,23 @@ __device__ __forceinline__ WaItem wa_item(const WinParams& p, int nitems) {
   return it;
 }
 
+// DropPath skip (mdemi_winattn_desc.sample_live): the sample of this wave's window is dead.
+// Wave-uniform -- a wave owns one (window, head) and a window lies in one sample -- and the
+// waves of a workgroup meet at no workgroup barrier (wave_lds_sync above), so a dead wave
+// writes its zeros and returns while its neighbours run on.
+__device__ __forceinline__ bool wa_dead(const WinParams& p, const WaItem& it, int b) {
+  return p.live && it.active && p.live[b] == 0.f;
+}
+// zeros to columns [col0, col0 + WA_HD) of the rows of the window's real tokens
+__device__ __forceinline__ void wa_zero_rows(const WinGeom& g, const Win<7>& w, float* base, int64_t ld, int col0,
+                                             int lane) {
+  for (int e = lane; e < WA_N * (WA_HD / 4); e += 64) {
+    const int row = w.row(g, e >> 3);
+    if (row >= 0)
+      *reinterpret_cast<float4*>(base + (int64_t)row * ld + col0 + 4 * (e & 7)) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
 // per-wave region ids (shift mask) and "needs mask" flag
 __device__ __forceinline__ bool wa_regions(const WinParams& p, const Win<7>& w, int8_t* reg, int lane) {
   const bool border = p.g.shift > 0 && (w.wy == p.g.nWh - 1 || w.wx == p.g.nWw - 1);
@@ -228,6 +246,11 @@ __global__ __launch_bounds__(256) void winattn_fwd_kernel(WinParams p, const flo
   const WaItem it = wa_item(p, nitems);
   const Win<WS> w(g, it.win);
   const int col0 = it.hh * HD;
+  if (wa_dead(p, it, w.b)) {
+    wa_zero_rows(g, w, p.out, p.out_ld, col0, lane);
+    if (p.lse && lane < WA_N) p.lse[(int64_t)it.item * WA_N + lane] = 0.f;
+    return;
+  }
   for (int e = lane; e < WA_NP * HD / 4; e += 64) {
     const int tok = e >> 3, c4 = e & 7;
     const float4 v = tok < WA_N ? ld_tok4(p.v, p.v_ld, w.row(g, tok), p.v_pad, col0 + 4 * c4)
@@ -414,6 +437,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WA_BWD_OCC,
   const WaItem it = wa_item(p, nitems);
   const Win<WS> w(g, it.win);
   const int col0 = it.hh * HD;
+  if (wa_dead(p, it, w.b)) {  // what a zero dout gives: zero dq / dk / dv rows, zero partials
+    wa_zero_rows(g, w, p.dq, p.dqk_ld, col0, lane);
+    wa_zero_rows(g, w, p.dk, p.dqk_ld, col0, lane);
+    wa_zero_rows(g, w, p.dv, p.dv_ld, col0, lane);
+    float* P = p.partial + (int64_t)it.item * (WA_T + 2 * HD);
+    for (int e = lane; e < WA_T + 2 * HD; e += 64) P[e] = 0.f;
+    return;
+  }
   // the saved log-sum-exp of this lane's two query columns, first: the softmax gradient waits on it
   float lse[2];
 #pragma unroll
@@ -697,6 +728,7 @@ static int make_params(const mdemi_winattn_desc* d, WinParams& p, int& nwin) {
   p.lse = d->lse;
   p.dout = d->dout; p.dq = d->dq; p.dk = d->dk; p.dqk_ld = d->dqk_ld; p.dv = d->dv; p.dv_ld = d->dv_ld;
   p.partial = (float*)d->workspace;
+  p.live = d->sample_live;
   {
     const int64_t rows = (int64_t)d->B * d->H * d->W;
     const int64_t lds[4] = {d->qk_ld, d->out_ld, d->dqk_ld, d->dv_ld};

@@ -65,6 +65,8 @@ class GemmDesc(ctypes.Structure):
         ("batch_inner", i32), ("_pad1", i32),
         ("a_bstride_inner", i64), ("b_bstride_inner", i64), ("c_bstride_inner", i64),
         ("row_scale", vp), ("row_scale_group", i64),
+        ("m_live", vp), ("m_live_group", i64),
+        ("k_live", vp), ("k_live_group", i64),
     ]
 
 
@@ -85,6 +87,7 @@ class WinAttnDesc(ctypes.Structure):
         ("d_rpb_table", vp),
         ("dq_pad", vp), ("dk_pad", vp), ("dv_pad", vp),
         ("workspace", vp), ("workspace_bytes", i64),
+        ("sample_live", vp),
     ]
 
 

@@ -274,8 +274,11 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_layout, b_layout, a_op=L.OP_NONE,
          alpha=1.0, beta=0.0, bias=None, bias_mode=L.BIAS_NONE, act=L.ACT_NONE, aux=None, ldaux=0,
          residual=None, ldres=0, batch=1, a_bstride=0, b_bstride=0, c_bstride=0, aux_bstride=0,
          res_bstride=0, split_k=None, conv=None, preact=None, ldpre=0, pre_bstride=0, rowsum_a=None,
-         a_off=0, b_off=0, c_off=0, inner=None, row_scale=None, row_scale_group=0, a16=None, b16=None, c16=None):
+         a_off=0, b_off=0, c_off=0, inner=None, row_scale=None, row_scale_group=0, a16=None, b16=None, c16=None,
+         m_live=None, k_live=None):
     """a_off/b_off/c_off: element offsets into A/B/C (column slices of wider buffers).
+    m_live / k_live: per-sample liveness mask [B] over the rows of C / the reduction index
+    (mdemi_gemm_desc.m_live / k_live; groups of M / B rows, K / B reduction steps).
     inner=(n, a_bstride_inner, b_bstride_inner, c_bstride_inner): a two-level batch of
     batch = outer * n entries (mdemi_gemm_desc.batch_inner), e.g. (image, head).
     a16 / b16 / c16 (precision "bf16" only): bf16 copies of A / B (the RNE bf16 of the fp32
@@ -314,6 +317,10 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_layout, b_layout, a_op=L.OP_NONE,
         d.rowsum_a = rowsum_a.data_ptr()
     if row_scale is not None:
         d.row_scale, d.row_scale_group = row_scale.data_ptr(), row_scale_group
+    if m_live is not None:
+        d.m_live, d.m_live_group = m_live.data_ptr(), M // m_live.numel()
+    if k_live is not None:
+        d.k_live, d.k_live_group = k_live.data_ptr(), K // k_live.numel()
     lib = L.load()
     need = lib.mdemi_gemm_workspace_size(ctypes.byref(d))
     if need:
@@ -400,9 +407,10 @@ def colsum(x2d, out=None, accumulate=False):
 
 
 def linear_fwd_raw(x2, weight, bias, in_gelu=False, residual=None, act=L.ACT_NONE, out=None, drop_scale=None,
-                   c16=None):
+                   c16=None, live=None):
     """drop_scale: per-sample DropPath scale [B] of the product (rows grouped M / B per sample),
-    applied in the epilogue before the residual add; c16: the output's bf16 copy (gemm())."""
+    applied in the epilogue before the residual add; c16: the output's bf16 copy (gemm());
+    live: per-sample liveness mask [B] of the output rows (gemm() m_live)."""
     M, K = x2.shape
     N = weight.shape[0]
     if out is None:
@@ -412,7 +420,7 @@ def linear_fwd_raw(x2, weight, bias, in_gelu=False, residual=None, act=L.ACT_NON
          bias=bias, bias_mode=L.BIAS_COL if bias is not None else L.BIAS_NONE, act=act,
          residual=residual, ldres=(residual.stride(0) if residual is not None else 0), split_k=1,
          row_scale=drop_scale, row_scale_group=(M // drop_scale.numel() if drop_scale is not None else 0),
-         c16=c16)
+         c16=c16, m_live=live)
     return out
 
 
@@ -426,19 +434,21 @@ def _drop_rows(dy2, scale):
 
 class _LinearFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, residual, in_gelu, drop_scale, out_b16=False):
+    def forward(ctx, x, weight, bias, residual, in_gelu, drop_scale, out_b16=False, live=None):
         _require_cuda(x, weight, bias, residual)
         K = x.shape[-1]
         x2 = _c(x).reshape(-1, K)
         res2 = _c(residual).reshape(x2.shape[0], -1) if residual is not None else None
         out = torch.empty(x2.shape[0], weight.shape[0], device=x.device, dtype=torch.float32)
         o16 = new_b16_like(out) if out_b16 else None  # the output feeds bf16 GEMMs (attention products)
-        linear_fwd_raw(x2, _c(weight), bias, in_gelu=in_gelu, residual=res2, drop_scale=drop_scale, out=out, c16=o16)
+        linear_fwd_raw(x2, _c(weight), bias, in_gelu=in_gelu, residual=res2, drop_scale=drop_scale, out=out, c16=o16,
+                       live=live)
         if o16 is not None:
             set_b16(out, o16)
         ctx.save_for_backward(x2, weight)
         ctx.dx16 = grad_feeds_gemm(x)
         ctx.drop_scale = drop_scale
+        ctx.live = live
         ctx.in_gelu = in_gelu
         ctx.has_bias = bias is not None
         ctx.has_res = residual is not None
@@ -460,7 +470,7 @@ class _LinearFn(torch.autograd.Function):
             # dX[M,K] = dY[M,N] . W[N,K]  (times gelu'(h) when the forward read gelu(h))
             gemm(dy2, weight, dx, M, K, N, lda=N, ldb=K, ldc=K, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG,
                  act=L.ACT_GELU_GRAD if ctx.in_gelu else L.ACT_NONE, aux=x2 if ctx.in_gelu else None,
-                 ldaux=K, c16=dx16)
+                 ldaux=K, c16=dx16, m_live=ctx.live)
             if dx16 is not None:
                 set_b16(dx, dx16)
             dx = dx.view(ctx.xshape)
@@ -471,29 +481,32 @@ class _LinearFn(torch.autograd.Function):
             dw = torch.empty(N, K, device=dy.device, dtype=torch.float32)
             # dW[N,K] = dY^T . X  (reduction over the M rows; split-K slabs); db = dY^T 1 rides along
             gemm(dy2, x2, dw, N, K, M, lda=N, ldb=K, ldc=K, a_layout=L.L_MNCONTIG, b_layout=L.L_MNCONTIG,
-                 b_op=L.OP_GELU if ctx.in_gelu else L.OP_NONE, rowsum_a=db)
+                 b_op=L.OP_GELU if ctx.in_gelu else L.OP_NONE, rowsum_a=db, k_live=ctx.live)
         elif want_db:
             colsum(dy2, out=db)
         dres = dy if ctx.has_res and ctx.needs_input_grad[3] else None
-        return dx, dw, db, dres, None, None, None
+        return dx, dw, db, dres, None, None, None, None
 
 
 def linear(x, weight, bias=None, residual=None, in_gelu=False, drop_scale=None, p=0.0, training=False,
-           out_b16=False):
+           out_b16=False, live=None):
     """y = (gelu(x) if in_gelu else x) @ W^T + b (+ residual); drop_scale (DropPath, per
     sample [B]): y = residual + drop_scale[sample] * (x @ W^T + b), fused in the epilogue.
     p > 0 and training: y = dropout(x @ W^T + b) (+ residual) -- nn.Dropout on a projection's
     output before a residual add (luna_layer.py:172-173,250-251, self_attention.py:78-80); the
     residual add is then a separate sweep after the dropout one.  out_b16 (no dropout): the
-    output's bf16 copy from the epilogue, for bf16 GEMMs that read it (bf16 storage)."""
+    output's bf16 copy from the epilogue, for bf16 GEMMs that read it (bf16 storage).
+    live (no dropout; per sample [B], an entry == 0 marks a dead sample): the caller needs
+    neither a dead sample's output rows nor anything its output gradient would contribute --
+    that gradient is exactly zero there -- so the GEMMs may skip them (gemm() m_live / k_live)."""
     if drop_scale is not None and residual is None:
         raise ValueError("linear: drop_scale scales a residual branch and needs residual")
     if training and p > 0.0:
-        if drop_scale is not None:
-            raise ValueError("linear: dropout and drop_scale together are not supported")
+        if drop_scale is not None or live is not None:
+            raise ValueError("linear: dropout and drop_scale / live together are not supported")
         y = dropout(_LinearFn.apply(x, weight, bias, None, in_gelu, None, False), p, True)
         return add(residual, y) if residual is not None else y
-    return _LinearFn.apply(x, weight, bias, residual, in_gelu, drop_scale, out_b16)
+    return _LinearFn.apply(x, weight, bias, residual, in_gelu, drop_scale, out_b16, live)
 
 
 class _MlpFn(torch.autograd.Function):
@@ -509,7 +522,7 @@ class _MlpFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, residual, cfg):
-        act, p_mid, p_out, seed, drop_scale = cfg
+        act, p_mid, p_out, seed, drop_scale, live = cfg  # live: mlp()
         _require_cuda(x, w1, b1, w2, b2, residual)
         K = x.shape[-1]
         x2 = _c(x).reshape(-1, K)
@@ -520,7 +533,7 @@ class _MlpFn(torch.autograd.Function):
         g16 = new_b16_like(g) if g.numel() % 4 == 0 else None  # fc2's operand (bf16 storage)
         gemm(x2, _c(w1), g, M, Hd, K, lda=K, ldb=K, ldc=Hd, a_layout=L.L_KCONTIG, b_layout=L.L_KCONTIG,
              bias=b1, bias_mode=L.BIAS_COL if b1 is not None else L.BIAS_NONE, act=act,
-             preact=h, ldpre=Hd, split_k=1, c16=g16 if p_mid == 0.0 else None)
+             preact=h, ldpre=Hd, split_k=1, c16=g16 if p_mid == 0.0 else None, m_live=live)
         if p_mid > 0.0:
             _drop(g.data_ptr(), g.data_ptr(), g.numel(), p_mid, seed, dst16_ptr=L.ptr(g16))
         if g16 is not None:
@@ -533,7 +546,7 @@ class _MlpFn(torch.autograd.Function):
                 L.call("mdemi_elementwise", L.EW_ADD, out.data_ptr(), res2.data_ptr(), out.data_ptr(), out.numel(),
                        0.0, 0.0, L.stream())
         else:
-            out = linear_fwd_raw(g, _c(w2), b2, residual=res2, drop_scale=drop_scale)
+            out = linear_fwd_raw(g, _c(w2), b2, residual=res2, drop_scale=drop_scale, live=live)
         ctx.save_for_backward(x2, w1, w2, h, g)
         ctx.flags = (b1 is not None, b2 is not None, residual is not None)
         ctx.cfg = cfg
@@ -544,7 +557,7 @@ class _MlpFn(torch.autograd.Function):
     def backward(ctx, dy):
         x2, w1, w2, h, g = ctx.saved_tensors
         has_b1, has_b2, has_res = ctx.flags
-        act, p_mid, p_out, seed, drop_scale = ctx.cfg
+        act, p_mid, p_out, seed, drop_scale, live = ctx.cfg
         M, K = x2.shape
         Hd, N = w1.shape[0], w2.shape[0]
         dy2 = _c(dy).reshape(M, N)
@@ -561,8 +574,9 @@ class _MlpFn(torch.autograd.Function):
             d2 = dy2
         dw2 = torch.empty(N, Hd, device=dev, dtype=torch.float32)
         db2 = torch.empty(N, device=dev, dtype=torch.float32) if has_b2 else None
+        # with `live`, d2 = 0 * dy on the dead samples' rows, so dh below is zero there too
         gemm(d2, g, dw2, N, Hd, M, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_MNCONTIG, b_layout=L.L_MNCONTIG,
-             rowsum_a=db2)
+             rowsum_a=db2, k_live=live)
         dh = torch.empty(M, Hd, device=dev, dtype=torch.float32)
         if p_mid > 0.0:
             gemm(d2, w2, dh, M, Hd, N, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG)
@@ -572,33 +586,40 @@ class _MlpFn(torch.autograd.Function):
         else:
             dh16 = new_b16_like(dh)  # the operand of both fc1 gradient GEMMs
             gemm(d2, w2, dh, M, Hd, N, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG,
-                 act=L.ACT_GRAD_OF[act], aux=h, ldaux=Hd, c16=dh16)
+                 act=L.ACT_GRAD_OF[act], aux=h, ldaux=Hd, c16=dh16, m_live=live)
             if dh16 is not None:
                 set_b16(dh, dh16)
         del h, g
         dw1 = torch.empty(Hd, K, device=dev, dtype=torch.float32)
         db1 = torch.empty(Hd, device=dev, dtype=torch.float32) if has_b1 else None
         gemm(dh, x2, dw1, Hd, K, M, lda=Hd, ldb=K, ldc=K, a_layout=L.L_MNCONTIG, b_layout=L.L_MNCONTIG,
-             rowsum_a=db1)
+             rowsum_a=db1, k_live=live)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, device=dev, dtype=torch.float32)
-            gemm(dh, w1, dx, M, K, Hd, lda=Hd, ldb=K, ldc=K, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG)
+            gemm(dh, w1, dx, M, K, Hd, lda=Hd, ldb=K, ldc=K, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG,
+                 m_live=live)
             dx = dx.view(ctx.xshape)
         dres = dy if has_res and ctx.needs_input_grad[5] else None
         return dx, dw1, db1, dw2, db2, dres, None
 
 
-def mlp(x, w1, b1, w2, b2, residual=None, act=L.ACT_GELU, p_mid=0.0, p_out=0.0, training=False, drop_scale=None):
+def mlp(x, w1, b1, w2, b2, residual=None, act=L.ACT_GELU, p_mid=0.0, p_out=0.0, training=False, drop_scale=None,
+        live=None):
     """fc2(dropout(act(fc1(x)))) -> dropout (+ residual); act GELU (exact erf), SiLU or ReLU.
     drop_scale (DropPath, per sample [B]): residual + drop_scale[sample] * branch, fused in
-    fc2's epilogue (no output dropout with it)."""
+    fc2's epilogue (no output dropout with it).  live (= drop_scale, no dropout; see
+    drop_live): a dropped sample's branch needs no fc1 / fc2 work, forward or backward -- its
+    gradient is exactly zero from fc2's output back to the branch input -- so all six GEMMs
+    may skip it (gemm() m_live / k_live)."""
     if not training:
         p_mid = p_out = 0.0
     if drop_scale is not None and (residual is None or p_out > 0.0):
         raise ValueError("mlp: drop_scale needs a residual and no output dropout")
     seed = _draw_seed(x.device) if (p_mid > 0.0 or p_out > 0.0) else None
-    return _MlpFn.apply(x, w1, b1, w2, b2, residual, (act, float(p_mid), float(p_out), seed, drop_scale))
+    if live is not None and (live is not drop_scale or p_mid > 0.0 or p_out > 0.0):
+        raise ValueError("mlp: live is the drop_scale tensor itself, without dropout")
+    return _MlpFn.apply(x, w1, b1, w2, b2, residual, (act, float(p_mid), float(p_out), seed, drop_scale, live))
 
 
 # --------------------------------------------------------------------------
@@ -952,7 +973,7 @@ class _WindowAttnFn(torch.autograd.Function):
     column v_off).  Pad tokens read qk_bias / v_bias (None -> zeros)."""
 
     @staticmethod
-    def forward(ctx, qk, qk_bias, v, v_bias, rpb, geom):
+    def forward(ctx, qk, qk_bias, v, v_bias, rpb, geom, live=None):
         _require_cuda(qk, qk_bias, v, v_bias, rpb)
         B, H, W, heads, window, shift, scale, C, v_off = geom
         rows = B * H * W
@@ -971,6 +992,8 @@ class _WindowAttnFn(torch.autograd.Function):
         nwin = B * (-(-H // ws)) * (-(-W // ws))
         lse = torch.empty(nwin, heads, ws * ws, device=qk.device, dtype=torch.float32)
         d.lse = lse.data_ptr()
+        d.sample_live = L.ptr(live)
+        ctx.live = live
         lib = L.load()
         # the forward's workspace is the expanded relative-position bias: a buffer of this call's
         # own (heads x 16 KiB), kept for the backward instead of expanding the table again
@@ -1029,6 +1052,7 @@ class _WindowAttnFn(torch.autograd.Function):
         d.dv, d.dv_ld = dv_t.data_ptr() + 4 * v_off, dv_t.stride(0)
         d.d_rpb_table = d_rpb.data_ptr()
         d.dq_pad, d.dk_pad, d.dv_pad = pad_g[0].data_ptr(), pad_g[1].data_ptr(), pad_g[2].data_ptr()
+        d.sample_live = L.ptr(ctx.live)
         lib = L.load()
         need = lib.mdemi_winattn_bwd_workspace_size(ctypes.byref(d))
         ws = L.workspace(need, qk.device)
@@ -1046,18 +1070,20 @@ class _WindowAttnFn(torch.autograd.Function):
             dv_bias = torch.zeros_like(v_bias)
             dv_bias[v_off:v_off + C] = pad_g[2]
         if same:
-            return dqk, dqk_bias, None, None, d_rpb, None
-        return dqk, dqk_bias, dv_t, dv_bias, d_rpb, None
+            return dqk, dqk_bias, None, None, d_rpb, None, None
+        return dqk, dqk_bias, dv_t, dv_bias, d_rpb, None, None
 
 
-def window_attention(qk, qk_bias, v, v_bias, rpb_table, B, H, W, heads, window, shift, scale, C, v_off=0):
+def window_attention(qk, qk_bias, v, v_bias, rpb_table, B, H, W, heads, window, shift, scale, C, v_off=0, live=None):
     """Swin: qk = v = qkv output [rows,3C], qk_bias = v_bias = qkv.bias, v_off = 2C.
-    NeW-CRF: qk = qk output [rows,2C] with its bias; v [rows,C] padded with zeros (v_bias None)."""
+    NeW-CRF: qk = qk output [rows,2C] with its bias; v [rows,C] padded with zeros (v_bias None).
+    live (per sample [B], entry == 0: dead): a dead sample's output rows come out zero and its
+    output gradient is taken as zero (mdemi_winattn_desc.sample_live)."""
     geom = (B, H, W, heads, window, shift, float(scale), C, v_off)
     if v is qk:
         # one tensor feeds q, k and v: pass it once so autograd sums its gradient
-        return _WindowAttnFn.apply(qk, qk_bias, qk, qk_bias if v_bias is not None else None, rpb_table, geom)
-    return _WindowAttnFn.apply(qk, qk_bias, v, v_bias, rpb_table, geom)
+        return _WindowAttnFn.apply(qk, qk_bias, qk, qk_bias if v_bias is not None else None, rpb_table, geom, live)
+    return _WindowAttnFn.apply(qk, qk_bias, v, v_bias, rpb_table, geom, live)
 
 
 # --------------------------------------------------------------------------
@@ -1527,6 +1553,27 @@ def drop_path_scale(batch, drop_prob, device):
     """timm DropPath's per-sample scale: bernoulli(keep) / keep, drawn on the device."""
     keep = 1.0 - drop_prob
     return torch.empty(batch, device=device, dtype=torch.float32).bernoulli_(keep).div_(keep)
+
+
+# DropPath skip: a dropped sample's branch (scale 0) adds nothing to the step, forward or
+# backward, so the Swin blocks hand the scale tensor to their GEMMs and window attention as a
+# liveness mask and the kernels skip that sample's work on the device (DESIGN.md "DropPath
+# skip").  Off: no mask is passed anywhere.  Default: env MDEMI_DROP_SKIP, on unless 0.
+_DROP_SKIP = [os.environ.get("MDEMI_DROP_SKIP", "1") != "0"]
+
+
+def set_drop_skip(on):
+    _DROP_SKIP[0] = bool(on)
+
+
+def get_drop_skip():
+    return _DROP_SKIP[0]
+
+
+def drop_live(scale):
+    """The liveness mask a DropPath scale tensor [B] serves as (entry == 0: dead sample), or
+    None when the skip is switched off.  The tensor is only ever read on the device."""
+    return scale if _DROP_SKIP[0] else None
 
 
 def drop_path_add(res, branch, drop_prob, training):

@@ -45,7 +45,7 @@ class Mlp(nn.Module):
 
     def forward(self, x, residual=None, drop_scale=None):
         return mf.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, residual=residual,
-                      drop_scale=drop_scale)
+                      drop_scale=drop_scale, live=mf.drop_live(drop_scale))
 
 
 class WindowAttention(nn.Module):
@@ -67,12 +67,14 @@ class WindowAttention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02)
 
-    def attend(self, xn, B, H, W, shift):
-        """xn: normed tokens [B*H*W, C] in natural order -> attention output (pre-proj) [B*H*W, C]."""
-        qkv = mf.linear(xn, self.qkv.weight, self.qkv.bias)
+    def attend(self, xn, B, H, W, shift, live=None):
+        """xn: normed tokens [B*H*W, C] in natural order -> attention output (pre-proj) [B*H*W, C].
+        live: per-sample mask [B] of the samples whose output is needed (mf.drop_live)."""
+        qkv = mf.linear(xn, self.qkv.weight, self.qkv.bias, live=live)
         C = self.dim
         return mf.window_attention(qkv, self.qkv.bias, qkv, self.qkv.bias, self.relative_position_bias_table, B, H,
-                                   W, self.num_heads, self.window_size[0], shift, self.scale, C, v_off=2 * C)
+                                   W, self.num_heads, self.window_size[0], shift, self.scale, C, v_off=2 * C,
+                                   live=live)
 
 
 class SwinTransformerBlock(nn.Module):
@@ -104,15 +106,19 @@ class SwinTransformerBlock(nn.Module):
         x2 = x.reshape(B * Lq, C)
         # layer_norm_skip: (LN(x), x) -- the residual's gradient is summed inside the LN backward
         xn, x2 = mf.layer_norm_skip(x2, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-        a = self.attn.attend(xn, B, H, W, self.shift_size)
         p = self.drop_path_prob if self.training else 0.0
         if p == 0.0:
+            a = self.attn.attend(xn, B, H, W, self.shift_size)
             x2 = mf.linear(a, self.attn.proj.weight, self.attn.proj.bias, residual=x2)
             xn, x2 = mf.layer_norm_skip(x2, self.norm2.weight, self.norm2.bias, self.norm2.eps)
             x2 = self.mlp(xn, residual=x2)
         else:  # DropPath (swin_transformer.py:232,239): the per-sample scale rides in the proj / fc2 epilogues
+            # s1 is drawn before the branch it scales so the branch can skip the dropped samples
+            # (attend draws nothing: the generator stream is s1, s2 per block either way)
             s1 = mf.drop_path_scale(B, p, x.device)
-            x2 = mf.linear(a, self.attn.proj.weight, self.attn.proj.bias, residual=x2, drop_scale=s1)
+            live = mf.drop_live(s1)
+            a = self.attn.attend(xn, B, H, W, self.shift_size, live=live)
+            x2 = mf.linear(a, self.attn.proj.weight, self.attn.proj.bias, residual=x2, drop_scale=s1, live=live)
             xn, x2 = mf.layer_norm_skip(x2, self.norm2.weight, self.norm2.bias, self.norm2.eps)
             s2 = mf.drop_path_scale(B, p, x.device)
             x2 = self.mlp(xn, residual=x2, drop_scale=s2)

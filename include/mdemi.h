@@ -52,6 +52,7 @@ int mdemi_version(void);
 /*                                                                          */
 /*   C[b][i][j] = act( alpha * sum_k A(b,i,k) * B(b,k,j) + bias + beta*C )   */
 /*                (+ residual[b][i][j])                                       */
+/* beta == 0 never reads C: its old contents, NaN included, do not matter.   */
 /* ------------------------------------------------------------------------ */
 
 /* operand layouts */

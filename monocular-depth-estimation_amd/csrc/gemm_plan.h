@@ -159,8 +159,9 @@ struct GemmPlan {
   int ktile_per_split, m_split;
   int64_t nblocks;
   size_t slab_bytes, rowsum_bytes;  // split-K slabs [split][batch][M - m_split][N]; row-sum partials [split][M]
-  bool deep;  // deep split with a plain store epilogue: combine by column sums (misc.hip; its
-              // workspace, colsum_ws_bytes(split, M * N), follows the two above)
+  bool deep;  // deep split with a plain store epilogue (no epilogue stage at all, row_scale
+              // included): combine by column sums (misc.hip; its workspace,
+              // colsum_ws_bytes(split, M * N), follows the two above)
 };
 inline GemmPlan plan_gemm(const mdemi_gemm_desc* d, int mode, int variant, int cus, const GemmOptions& o) {
   const GemmVariant& e = variant_table(mode).v[variant];
@@ -186,7 +187,7 @@ inline GemmPlan plan_gemm(const mdemi_gemm_desc* d, int mode, int variant, int c
     g.slab_bytes = (slab + 255) / 256 * 256;
     g.rowsum_bytes = d->rowsum_a ? (size_t)g.split * d->M * sizeof(float) : 0;
     g.deep = g.split >= 32 && d->batch == 1 && d->alpha == 1.f && d->beta == 0.f && d->bias_mode == MDEMI_BIAS_NONE &&
-             d->act == MDEMI_ACT_NONE && !d->residual && !d->preact && d->ldc == d->N;
+             d->act == MDEMI_ACT_NONE && !d->residual && !d->preact && !d->row_scale && d->ldc == d->N;
   }
   return g;
 }

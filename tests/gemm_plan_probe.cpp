@@ -1,7 +1,8 @@
 // Host probe of csrc/gemm_plan.h for the CPU tests (tests/gemm_plan_util.py builds it with the
 // host compiler, -Iinclude only): prints what the launcher's own plan and raster code compute.
 //   jobs tiles_m1 tiles_m tiles_n batch split group_m -> "b sidx tm tn" per workgroup id
-//   plan M N K batch split_k cus                     -> one line per mode and variant legal for it
+//   plan M N K batch split_k cus [row_scale]         -> one line per mode and variant legal for it
+//                                                       (row_scale 1: the descriptor carries a row_scale)
 //   tail M N K cus                                   -> "m_split split" of tail_plan
 //   tables                                           -> "mode n" and the autotune candidates per mode,
 //                                                       for operands that can / cannot be DMA-staged
@@ -36,8 +37,10 @@ int main(int argc, char** argv) {
       const GemmJob j = job_of(g, bid);
       printf("%d %d %d %d\n", j.b, j.sidx, j.tm, j.tn);
     }
-  } else if (!strcmp(argv[1], "plan") && argc == 8) {
-    const mdemi_gemm_desc d = dense(a[0], a[1], a[2], a[3], a[4]);
+  } else if (!strcmp(argv[1], "plan") && (argc == 8 || argc == 9)) {
+    mdemi_gemm_desc d = dense(a[0], a[1], a[2], a[3], a[4]);
+    static const float scale[1] = {1.f};
+    if (a[6]) { d.row_scale = scale; d.row_scale_group = d.M; }
     for (int mode : modes)
       for (int v = 0; v < variant_table(mode).n; ++v) {
         const GemmVariant& e = variant_table(mode).v[v];

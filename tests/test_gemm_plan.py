@@ -17,8 +17,8 @@ CASES = ([(M, N, K, 1, s) for (M, N, K) in SHAPES for s in (1, 4, 5)]
 NVARIANTS = {GEMM_F32: 13, GEMM_BF16: 5, GEMM_F32E: 5, GEMM_B16: 3}  # table lengths (fp32e shares the 16-bit table)
 
 
-def plans(M, N, K, batch, split_k, cus=CUS):
-    return [dict(zip(COLS, r)) for r in probe("plan", M, N, K, batch, split_k, cus)]
+def plans(M, N, K, batch, split_k, cus=CUS, row_scale=0):
+    return [dict(zip(COLS, r)) for r in probe("plan", M, N, K, batch, split_k, cus, row_scale)]
 
 
 def test_tables_and_autotune_candidates():
@@ -65,6 +65,17 @@ def test_plan_invariants(case):
         assert first["slab_bytes"] >= first["split"] * batch * (M - first["m_split"]) * N * 4
     else:
         assert first["slab_bytes"] == 0
+
+
+def test_deep_combine_leaves_row_scale_to_the_epilogue():
+    """split_k = 33 over the 33 chunks of K = 1056 with a plain store takes the deep column-sum
+    combine; the same descriptor with a row_scale must not, because column sums apply no scale:
+    it keeps the slabs and the ordinary combine, and asks for no column-sum scratch."""
+    plain, scaled = plans(24, 40, 1056, 1, 33), plans(24, 40, 1056, 1, 33, row_scale=1)
+    assert len(plain) == len(scaled) > 0
+    for p, s in zip(plain, scaled):
+        assert p["split"] == s["split"] == 33 and p["deep"] == 1 and s["deep"] == 0, (p, s)
+        assert {k: v for k, v in p.items() if k != "deep"} == {k: v for k, v in s.items() if k != "deep"}
 
 
 @pytest.mark.parametrize("cus", [64, 256, 304])

@@ -422,6 +422,29 @@ int mdemi_adamw_step_dev_ema16(const mdemi_tensor_ref* tensors_dev, int32_t nten
                                float ema_decay, int32_t ema_warmup, mdemi_ema_state* ema_state_dev,
                                mdemi_guard_state* guard_dev, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Multi-scale gradient-matching loss (cfg loss.grad_weight / grad_scales;   */
+/* this framework's own definition, DESIGN.md 1c -- no reference parity).    */
+/* pred, gt [B][H][W]; R = log(pred) - log(gt) where gt > min_depth.  Scale  */
+/* k < scales (1..4) works on R[::s, ::s], s = 2^k: S_bk sums |R(y,x+s) -     */
+/* R(y,x)| and |R(y+s,x) - R(y,x)| over grid pairs valid at both ends, N_bk  */
+/* counts the valid grid pixels.  per_image 0: loss = sum_k sum_b S_bk /     */
+/* sum_b N_bk; 1: the mean over images with N_b0 > 0 of sum_k S_bk / N_bk;   */
+/* an empty scale adds 0, no valid pixel at all gives 0.                     */
+/* fwd writes loss[0] and wk [B][4] = dloss/dS_bk (0 for k >= scales); bwd:  */
+/* dpred = dloss[0] (device scalar) * sum_k wk[b][k] * c_k / pred with c_k   */
+/* the sum over the pixel's scale-k neighbours n of sign(R - R(n)), sign(0)  */
+/* = 0; exactly 0 where gt <= min_depth.  A gather without atomics: both     */
+/* passes are bit-deterministic.  Any H, W; rows that are 16-byte aligned    */
+/* (W % 4 == 0 and aligned bases) take the 4-pixel vector path.              */
+/* workspace: mdemi_gradmatch_workspace_size bytes, 16-byte aligned.         */
+/* ------------------------------------------------------------------------ */
+size_t mdemi_gradmatch_workspace_size(int32_t B, int32_t H, int32_t W);
+int mdemi_gradmatch_fwd(const float* pred, const float* gt, float* loss, float* wk, int32_t B, int32_t H, int32_t W,
+                        float min_depth, int32_t scales, int32_t per_image, void* workspace, void* stream);
+int mdemi_gradmatch_bwd(const float* pred, const float* gt, const float* wk, const float* dloss, float* dpred,
+                        int32_t B, int32_t H, int32_t W, float min_depth, int32_t scales, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

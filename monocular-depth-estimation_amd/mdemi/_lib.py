@@ -262,6 +262,9 @@ _SIGS = {
                                               vp, f32, i32, vp, vp, vp, vp]),
     "mdemi_adamw_step_dev_ema16": (ctypes.c_int, [vp, i32, vp, i32, i32, vp, vp, vp, f32, f32, i64, vp, vp, f32, i32,
                                                   vp, vp, vp, vp]),
+    "mdemi_gradmatch_workspace_size": (sz, [i32, i32, i32]),
+    "mdemi_gradmatch_fwd": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp]),
+    "mdemi_gradmatch_bwd": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]),
 }
 
 _lib = None

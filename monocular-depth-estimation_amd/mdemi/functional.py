@@ -1172,6 +1172,65 @@ def silog_loss(pred, gt, min_depth=1e-3, alpha=10.0, beta=0.15, per_image=False,
 
 
 # --------------------------------------------------------------------------
+# Multi-scale gradient-matching loss
+# --------------------------------------------------------------------------
+
+GRAD_MATCH_MAX_SCALES = 4  # the kernel's largest step is 2**3 = 8 pixels (csrc/gradmatch.hip)
+
+
+def check_grad_scales(scales, what="scales"):
+    if isinstance(scales, bool) or not isinstance(scales, int) or not 1 <= scales <= GRAD_MATCH_MAX_SCALES:
+        raise ValueError(f"{what} must be an integer 1..{GRAD_MATCH_MAX_SCALES}, got {scales!r}")
+    return scales
+
+
+class _GradMatchFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, min_depth, scales, per_image):
+        _require_cuda(pred, gt)
+        pred = _c(pred)
+        gt = _c(gt)
+        H, W = pred.shape[-2:]
+        B = pred.numel() // (H * W)
+        loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+        wk = torch.empty(B, GRAD_MATCH_MAX_SCALES, device=pred.device, dtype=torch.float32)
+        lib = L.load()
+        ws = L.workspace(lib.mdemi_gradmatch_workspace_size(B, H, W), pred.device, slot=4)
+        L.check(lib.mdemi_gradmatch_fwd(pred.data_ptr(), gt.data_ptr(), loss.data_ptr(), wk.data_ptr(), B, H, W,
+                                        float(min_depth), scales, int(per_image), ws.data_ptr(), L.stream()),
+                "gradmatch_fwd")
+        ctx.save_for_backward(pred, gt, wk)
+        ctx.cfg = (min_depth, scales)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, gt, wk = ctx.saved_tensors
+        min_depth, scales = ctx.cfg
+        H, W = pred.shape[-2:]
+        B = pred.numel() // (H * W)
+        dpred = torch.empty_like(pred)
+        dl = _c(dloss.reshape(1).to(torch.float32))
+        L.call("mdemi_gradmatch_bwd", pred.data_ptr(), gt.data_ptr(), wk.data_ptr(), dl.data_ptr(),
+               dpred.data_ptr(), B, H, W, float(min_depth), scales, L.stream())
+        return dpred, None, None, None, None
+
+
+def grad_match_loss(pred, gt, min_depth=1e-3, scales=4, per_image=False):
+    """Multi-scale, scale-invariant gradient-matching loss (MegaDepth / MiDaS) of pred against gt,
+    both (B,1,H,W) or (B,H,W): with R = log pred - log gt on gt > min_depth, the sum over the
+    ``scales`` grids R[::2**k, ::2**k] of the absolute differences of horizontally and vertically
+    adjacent valid grid pixels, divided by the number of valid grid pixels -- over the batch, or
+    per image and then averaged over the images that have a valid pixel."""
+    check_grad_scales(scales)
+    if pred.dim() < 3 or pred.shape != gt.shape or pred.numel() == 0 or \
+            pred.numel() != pred.shape[0] * pred.shape[-2] * pred.shape[-1]:
+        raise ValueError(f"grad_match_loss: pred and gt must both be (B,1,H,W) or (B,H,W) and non-empty, got "
+                         f"{tuple(pred.shape)} and {tuple(gt.shape)}")
+    return _GradMatchFn.apply(pred, gt, min_depth, scales, bool(per_image))
+
+
+# --------------------------------------------------------------------------
 # Resampling / layout
 # --------------------------------------------------------------------------
 

@@ -40,10 +40,24 @@ def _args(argv):
     ap.add_argument("--ema-decay", type=float, default=None,
                     help="override the config's train.ema_decay: keep an exponential moving average of the "
                          "weights with this decay, validate it and choose best.pth on it")
+    ap.add_argument("--grad-weight", type=float, default=None,
+                    help="override the config's loss.grad_weight: add this weight times the multi-scale "
+                         "gradient-matching loss to the training loss (0 switches the term off)")
     ap.add_argument("--ema", action="store_true",
                     help="with --test: evaluate the checkpoint's averaged weights (ema_state_dict)")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many optimizer steps (in all)")
     return ap.parse_args(argv)
+
+
+def _override(opt, args):
+    """The command line's overrides of config keys, written into opt."""
+    if args.nonfinite is not None:
+        opt.setdefault("train", {})["nonfinite"] = args.nonfinite
+    if args.ema_decay is not None:
+        opt.setdefault("train", {})["ema_decay"] = args.ema_decay
+    if args.grad_weight is not None:
+        opt.setdefault("loss", {})["grad_weight"] = args.grad_weight
+    return opt
 
 
 def _dataset(opt, mode, list_root):
@@ -91,15 +105,12 @@ def main(argv=None) -> int:
         rank, world, local_rank = 0, 1, 0
 
     # 1. the config
-    opt = parse(args.opt, write_option=rank == 0 and not args.test)
-    if args.nonfinite is not None:
-        opt.setdefault("train", {})["nonfinite"] = args.nonfinite
-    if args.ema_decay is not None:
-        opt.setdefault("train", {})["ema_decay"] = args.ema_decay
-    from .train.builder import nonfinite_policy
+    opt = _override(parse(args.opt, write_option=rank == 0 and not args.test), args)
+    from .train.builder import grad_match_config, nonfinite_policy
     from .train.ema import ema_config
     nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
     ema_config(opt)  # and so does a bad train.ema_decay / ema_warmup / ema_validate
+    grad_match_config(opt)  # and a bad loss.grad_weight / grad_scales
     if args.ema and not args.test:
         raise SystemExit("mdemi.run --ema selects the weights --test evaluates; to train with averaged weights set "
                          "train.ema_decay (or --ema-decay)")

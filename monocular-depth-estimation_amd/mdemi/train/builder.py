@@ -18,6 +18,11 @@ unchanged, onto this framework's objects:
                         ODA2: loss.si_weight x the mean SILog over every output the model returns
                         -- the head's earlier outputs get gradient from nowhere else, its
                         depth indices are detached, :246-253)
+  loss.grad_weight      -> absent / 0: off.  A finite float > 0: + grad_weight x GradMatchLoss, the
+                           multi-scale gradient-matching term on the same (resized) depth, per image
+                           or per batch as loss.per_image says; ODA2: averaged over every output
+                           like si_weight x SILog.  loss.grad_scales: its scales, 1..4 (default 4).
+                           This framework's own keys and definition (a decision)
   optimizer.lr/weight_decay/betas/eps/same_lr -> FusedAdamW; with get_1x_lr_params
                         (unet_adaptive_bins.py:111-117) and same_lr false: two groups,
                         encoder at lr/10, the rest at lr
@@ -50,7 +55,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .loss import BinsChamferLoss, SILogLoss
+from .loss import BinsChamferLoss, GradMatchLoss, SILogLoss, resize_to_gt
 from .optim import FusedAdamW, OneCycleLR
 
 MODEL_NAMES = ("adabins", "newcrfs", "depthformer_v8", "oda2_red_order_swin2")
@@ -97,12 +102,26 @@ def build_model(opt, drop_path=None):
 # loss.* keys of the in-scope reference configs; sog_weight names a loss term this framework
 # does not implement (0.0 in every in-scope config) and reduction_ratio configures only that
 # term -- a nonzero sog_weight is refused rather than silently dropped
-LOSS_KEYS = ("alpha", "beta", "per_image", "chamfer_weight", "si_weight", "sog_weight", "reduction_ratio")
+# grad_weight / grad_scales are this framework's own keys (the gradient-matching term)
+LOSS_KEYS = ("alpha", "beta", "per_image", "chamfer_weight", "si_weight", "sog_weight", "reduction_ratio",
+             "grad_weight", "grad_scales")
+
+
+def grad_match_config(opt):
+    """(loss.grad_weight, loss.grad_scales), validated: a finite weight >= 0 (absent: 0.0, the
+    term is off) and an integer number of scales 1..4 (default 4)."""
+    lo = opt.get("loss", {})
+    w = lo.get("grad_weight", 0.0)
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+        raise ValueError(f"loss.grad_weight must be a finite number >= 0, got {w!r}")
+    from ..functional import check_grad_scales
+    return float(w), check_grad_scales(lo.get("grad_scales", 4), "loss.grad_scales")
 
 
 class TrainLoss:
     """SILog on the depth (+ chamfer_weight x the bin chamfer loss on AdaBins' edges /
-    Depthformer's centres when loss.chamfer_weight > 0)."""
+    Depthformer's centres when loss.chamfer_weight > 0, + grad_weight x the multi-scale
+    gradient-matching loss on the same depth when loss.grad_weight > 0)."""
 
     def __init__(self, opt, model_name):
         lo = opt.get("loss", {})
@@ -112,23 +131,36 @@ class TrainLoss:
         if float(lo.get("sog_weight", 0.0)) != 0.0:
             raise ValueError(f"loss.sog_weight={lo['sog_weight']}: the SOG loss term is not implemented "
                              "(every in-scope reference config sets it to 0.0)")
+        self.grad_weight, grad_scales = grad_match_config(opt)
         dmin, _ = _depth_range(opt)
         self.silog = SILogLoss(alpha=float(lo.get("alpha", 10.0)), beta=float(lo.get("beta", 0.15)),
                                per_image=bool(lo.get("per_image", False)), min_depth=dmin)
         self.w = float(lo.get("chamfer_weight", 0.0))
         self.chamfer = BinsChamferLoss(dmin, from_edges=(model_name == "adabins")) if self.w > 0 else None
+        # weight 0 (or no key): no module, nothing of the term is launched
+        self.grad = GradMatchLoss(grad_scales, per_image=self.silog.per_image, min_depth=dmin) \
+            if self.grad_weight > 0 else None
         self.multi = model_name == "oda2_red_order_swin2"
         self.si_weight = float(lo.get("si_weight", 1.0))
 
     def __call__(self, out, gt):
         if self.multi:  # (out, outs, attn): every output, each upsampled to the GT
-            outs = out[1]
+            outs = [resize_to_gt(o, gt) for o in out[1]]
             loss = self.silog(outs[0], gt)
             for o in outs[1:]:
                 loss = loss + self.silog(o, gt)
-            return loss * (self.si_weight / len(outs))
+            loss = loss * (self.si_weight / len(outs))
+            if self.grad is not None:
+                gm = self.grad(outs[0], gt)
+                for o in outs[1:]:
+                    gm = gm + self.grad(o, gt)
+                loss = loss + gm * (self.grad_weight / len(outs))
+            return loss
         pred = out[0] if isinstance(out, tuple) else out
-        loss = self.silog(pred, gt)  # SILogLoss upsamples a half-resolution prediction to the GT first
+        pred = resize_to_gt(pred, gt)  # a half-resolution prediction, once for both terms
+        loss = self.silog(pred, gt)
+        if self.grad is not None:
+            loss = loss + self.grad_weight * self.grad(pred, gt)
         if self.chamfer is not None:
             loss = loss + self.w * self.chamfer(out[1], gt)
         return loss

@@ -3,10 +3,21 @@ the AdaBins bin chamfer loss (config key loss.chamfer_weight; restated from
 upstream AdaBins' BinsChamferLoss -- the reference's loss module is absent).
 AdaBins / Depthformer predictions are at half resolution and are resized to
 the ground truth with bilinear align_corners=True first (upstream AdaBins
-convention; parity unpinned)."""
+convention; parity unpinned).  The multi-scale gradient-matching loss (config keys
+loss.grad_weight / loss.grad_scales) is this framework's own term."""
 import torch.nn as nn
 
 from .. import functional as mf
+
+
+def resize_to_gt(pred, gt):
+    """pred (B,1,h,w) at the resolution of gt (B,1,H,W): itself when they agree, else bilinear
+    align_corners=True."""
+    if pred.shape[-2:] == gt.shape[-2:]:
+        return pred
+    B, _, h, w = pred.shape
+    return mf.interpolate_bilinear(pred.reshape(B, h, w, 1), size=tuple(gt.shape[-2:]),
+                                   align_corners=True).reshape(B, 1, *gt.shape[-2:])
 
 
 class SILogLoss(nn.Module):
@@ -17,11 +28,24 @@ class SILogLoss(nn.Module):
 
     def forward(self, pred, gt):
         """pred (B,1,h,w), gt (B,1,H,W) NCHW (C=1, so also NHWC)."""
-        if pred.shape[-2:] != gt.shape[-2:]:
-            B, _, h, w = pred.shape
-            pred = mf.interpolate_bilinear(pred.reshape(B, h, w, 1), size=tuple(gt.shape[-2:]),
-                                           align_corners=True).reshape(B, 1, *gt.shape[-2:])
-        return mf.silog_loss(pred, gt, self.min_depth, self.alpha, self.beta, self.per_image, self.unbiased)
+        return mf.silog_loss(resize_to_gt(pred, gt), gt, self.min_depth, self.alpha, self.beta, self.per_image,
+                             self.unbiased)
+
+
+class GradMatchLoss(nn.Module):
+    """Multi-scale, scale-invariant gradient-matching loss (MegaDepth / MiDaS / DPT): over
+    ``scales`` grids of step 1, 2, 4, 8 pixels, the absolute differences of log pred - log gt
+    between adjacent valid grid pixels, normalised by the valid grid pixels -- per batch or
+    per image, the switch SILog reads (one libmdemi sweep forward, one backward)."""
+
+    def __init__(self, scales=4, per_image=False, min_depth=1e-3):
+        super().__init__()
+        self.scales, self.per_image = mf.check_grad_scales(scales), bool(per_image)
+        self.min_depth = float(min_depth)
+
+    def forward(self, pred, gt):
+        """pred (B,1,h,w), gt (B,1,H,W); a half-resolution prediction is resized to the GT first."""
+        return mf.grad_match_loss(resize_to_gt(pred, gt), gt, self.min_depth, self.scales, self.per_image)
 
 
 class BinsChamferLoss(nn.Module):

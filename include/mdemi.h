@@ -150,6 +150,35 @@ typedef struct mdemi_gemm_desc {
 
 size_t mdemi_gemm_workspace_size(const mdemi_gemm_desc* d);
 int mdemi_gemm_f32(const mdemi_gemm_desc* d, void* stream);
+/* Two GEMMs in one call.  The effect equals mdemi_gemm_f32(d0) then mdemi_gemm_f32(d1), bit for
+ * bit, for every descriptor pair.  Where both members run a 128x128 direct-to-LDS variant
+ * (dense 16-B vectorisable operands, no load-time op, no conv operand, batch 1; layouts
+ * (KCONTIG, MNCONTIG) beside (MNCONTIG, MNCONTIG), in either order -- an input gradient and
+ * a weight gradient) and are independent, their grids run as one launch: each member keeps
+ * the plan it has alone (K split, tail split, raster), so no tile computes anything
+ * different, and a split member is combined after the launch as usual.  Every other pair
+ * runs as the two launches, in order.
+ * No-overlap rule: the members are independent when nothing one writes (C, preact, rowsum_a,
+ * its workspace) overlaps anything the other reads or writes, judged from the byte ranges the
+ * extents and leading dimensions give (column slices of one buffer with a common leading
+ * dimension do not overlap).  A pair that is not independent is not an error: it runs in order.
+ * Which of {two launches, one launch at variant 11, one launch at variant 8} is used is timed
+ * once per pair of shapes on first use outside a stream capture (during a capture with nothing
+ * cached: two launches).  MDEMI_GEMM_PAIR=0 in the environment turns pairing off;
+ * MDEMI_GEMM_PAIR_LOG=1 prints each timing to stderr, once per pair of shapes.
+ * Workspace: each descriptor carries its own; the two must not overlap.  One buffer of
+ * mdemi_gemm_pair_workspace_size(d0, d1) bytes serves both: member 0 at offset 0, member 1 at
+ * mdemi_gemm_pair_workspace_offset(d0) (member 0's size rounded up to 256 bytes). */
+int mdemi_gemm_f32_pair(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, void* stream);
+size_t mdemi_gemm_pair_workspace_size(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1);
+size_t mdemi_gemm_pair_workspace_offset(const mdemi_gemm_desc* d0);
+/* pairing switches (process-global): enabled 0 = always two launches; force_arm -1 = timed per
+ * pair of shapes (default), 0 = two launches, 1 / 2 = one launch at variant 11 / 8 wherever the
+ * pair is eligible (else two launches).  mdemi_gemm_pair_last_arm: the arm the last
+ * mdemi_gemm_f32_pair call ran (0, 1, 2; -1 before any call). */
+int mdemi_gemm_pair_set_options(int32_t enabled, int32_t force_arm);
+int mdemi_gemm_pair_enabled(void);
+int mdemi_gemm_pair_last_arm(void);
 /* Same contract with bf16 compute (mixed precision, BASELINE configs[4] "bf16"
  * = torch.autocast's matmul numerics): fp32 operands are rounded to bf16 (RNE)
  * as they are staged, products run on the bf16 MFMA with fp32 accumulation,

@@ -30,6 +30,7 @@
 #include "gemm_f32_kernel.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -271,6 +272,57 @@ struct B16Ext {
   const void* a16; const void* b16; void* c16;
 };
 
+// One GEMM made ready to launch: the plan, the kernel arguments and what follows the launch.
+// launch() runs it in a grid of its own; launch_pair() puts two of them into one grid.
+struct Prepared {
+  GemmPlan g;
+  GemmParams p;
+  float* rowsum_part;
+  bool deep;
+  int64_t counters;  // split-tile counters an in-launch combine needs (0: combined after the launch)
+};
+
+// everything of launch() up to the counters and the kernel choice
+static int prepare(const mdemi_gemm_desc* d, int variant, int mode, const B16Ext* ext, Prepared& r) {
+  r.g = plan_for(d, mode, variant);
+  const GemmPlan& g = r.g;
+  GemmParams& p = r.p;
+  fill_params(d, g, p);
+  if (ext) {
+    p.c16 = ext->c16;
+    if (mode == GEMM_B16) {  // the kernel reads the bf16 tensors through the A/B slots
+      p.A = reinterpret_cast<const float*>(ext->a16);
+      p.B = reinterpret_cast<const float*>(ext->b16);
+    }
+  }
+  r.rowsum_part = nullptr;
+  if (p.split > 1) {
+    const size_t need = plan_bytes(d, g);
+    if (!d->workspace || (size_t)d->workspace_bytes < need) {
+      set_error("gemm: split-K needs %zu workspace bytes", need);
+      return MDEMI_EWORKSPACE;
+    }
+    p.slab = (float*)d->workspace;
+    if (d->rowsum_a) {
+      r.rowsum_part = (float*)((char*)d->workspace + g.slab_bytes);
+      p.rowsum = r.rowsum_part;
+    }
+  }
+  MDEMI_REQUIRE(g.nblocks < (int64_t)1 << 31, "gemm: grid too large");
+  r.deep = g.deep && !p.c16;  // the column-sum combine writes fp32 only
+  // both bf16 families (bf16 operands in HBM, or rounded at staging) combine alike, so the
+  // bf16-storage step stays bit-identical to the fp32-operand bf16 step
+  const bool inline_reduce = (mode == GEMM_B16 || mode == GEMM_BF16) ? g_inline_reduce_b16 : g_inline_reduce;
+  r.counters = (p.split > 1 && !r.deep && (inline_reduce || p.m_split > 0)) ? (int64_t)p.tiles_m * p.tiles_n * d->batch : 0;
+  return MDEMI_OK;
+}
+// hands the split tiles their counters (null: none to be had, the reduce kernel combines)
+static void set_counters(const mdemi_gemm_desc* d, Prepared& r, int* cnt) {
+  r.p.tile_cnt = cnt;
+  if (cnt && r.rowsum_part) r.p.rowsum_out = d->rowsum_a;  // the last arrivers sum the row partials
+}
+static int finish(const mdemi_gemm_desc* d, const Prepared& r, hipStream_t st);
+
 static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mode, const B16Ext* ext = nullptr) {
   variant = resolve_variant(d, mode, variant);
   KernelFn fn = mode == GEMM_F32   ? pick_kernel(d->a_layout, d->b_layout, d->a_op, d->b_op, variant)
@@ -282,39 +334,20 @@ static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mod
               d->b_op);
     return MDEMI_EUNSUP;
   }
-  const GemmPlan g = plan_for(d, mode, variant);
-  GemmParams p;
-  fill_params(d, g, p);
-  if (ext) {
-    p.c16 = ext->c16;
-    if (mode == GEMM_B16) {  // the kernel reads the bf16 tensors through the A/B slots
-      p.A = reinterpret_cast<const float*>(ext->a16);
-      p.B = reinterpret_cast<const float*>(ext->b16);
-    }
-  }
-  float* rowsum_part = nullptr;
-  if (p.split > 1) {
-    const size_t need = plan_bytes(d, g);
-    if (!d->workspace || (size_t)d->workspace_bytes < need) {
-      set_error("gemm: split-K needs %zu workspace bytes", need);
-      return MDEMI_EWORKSPACE;
-    }
-    p.slab = (float*)d->workspace;
-    if (d->rowsum_a) {
-      rowsum_part = (float*)((char*)d->workspace + g.slab_bytes);
-      p.rowsum = rowsum_part;
-    }
-  }
-  MDEMI_REQUIRE(g.nblocks < (int64_t)1 << 31, "gemm: grid too large");
-  const bool deep = g.deep && !p.c16;  // the column-sum combine writes fp32 only
-  // both bf16 families (bf16 operands in HBM, or rounded at staging) combine alike, so the
-  // bf16-storage step stays bit-identical to the fp32-operand bf16 step
-  const bool inline_reduce = (mode == GEMM_B16 || mode == GEMM_BF16) ? g_inline_reduce_b16 : g_inline_reduce;
-  if (p.split > 1 && !deep && (inline_reduce || p.m_split > 0)) {
-    p.tile_cnt = tile_counters((int64_t)p.tiles_m * p.tiles_n * d->batch, st);
-    if (p.tile_cnt && rowsum_part) p.rowsum_out = d->rowsum_a;  // the last arrivers sum the row partials
-  }
-  hipLaunchKernelGGL(fn, dim3((unsigned)g.nblocks), dim3(GTHREADS), 0, st, p);
+  Prepared r;
+  if (int rc = prepare(d, variant, mode, ext, r)) return rc;
+  if (r.counters) set_counters(d, r, tile_counters(r.counters, st));
+  hipLaunchKernelGGL(fn, dim3((unsigned)r.g.nblocks), dim3(GTHREADS), 0, st, r.p);
+  if (int rc = finish(d, r, st)) return rc;
+  return check_launch(mode == GEMM_BF16 ? "gemm_bf16" : mode == GEMM_F32E ? "gemm_f32e" : mode == GEMM_B16 ? "gemm_bf16x" : "gemm_f32");
+}
+
+// the combine of a split GEMM whose pieces were not combined inside the launch
+static int finish(const mdemi_gemm_desc* d, const Prepared& r, hipStream_t st) {
+  const GemmPlan& g = r.g;
+  const GemmParams& p = r.p;
+  float* const rowsum_part = r.rowsum_part;
+  const bool deep = r.deep;
   if (p.split > 1 && !p.tile_cnt) {
     if (deep) {
       // many slabs over a small C (skinny weight gradients over ~10^6 pixels): a
@@ -331,7 +364,7 @@ static int launch(const mdemi_gemm_desc* d, int variant, hipStream_t st, int mod
                          rowsum_part ? d->rowsum_a : (float*)nullptr);
     }
   }
-  return check_launch(mode == GEMM_BF16 ? "gemm_bf16" : mode == GEMM_F32E ? "gemm_f32e" : mode == GEMM_B16 ? "gemm_bf16x" : "gemm_f32");
+  return MDEMI_OK;
 }
 
 struct TuneKey {
@@ -372,7 +405,11 @@ static int choose_variant(const mdemi_gemm_desc* d_in, hipStream_t st, int mode,
   if (!tunable(d, st)) return 0;
   if (ext && ext->c16 && (ext->c16 == ext->a16 || ext->c16 == ext->b16)) return 0;
   hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 0;
+  if (hipEventCreate(&e0) != hipSuccess) return 0;
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    return 0;
+  }
   int best = 0;
   float best_ms = 1e30f;
   for (int v = 0; v < variant_table(mode).n; ++v) {
@@ -454,6 +491,160 @@ extern "C" int mdemi_gemm_bf16x_supported(const mdemi_gemm_desc* d, const void* 
 extern "C" int mdemi_gemm_f32(const mdemi_gemm_desc* d, void* stream) { return gemm_entry(d, stream, GEMM_F32); }
 extern "C" int mdemi_gemm_bf16(const mdemi_gemm_desc* d, void* stream) { return gemm_entry(d, stream, GEMM_BF16); }
 extern "C" int mdemi_gemm_f32e(const mdemi_gemm_desc* d, void* stream) { return gemm_entry(d, stream, GEMM_F32E); }
+
+// ---------------------------------------------------------------------------------------------
+// Paired launch: two independent fp32 GEMMs in one grid (gemm_glds_kernel_pair).  Each member
+// keeps the plan plan_for() gives it alone -- K split, tail split, raster, split chunks -- and
+// its own combine after the launch, so every tile is the tile its own launch computes and
+// only the launch it runs in changes.  Which of {two launches, pair at variant 11, pair at
+// variant 8} runs is timed once per pair of shapes; all three are bit-identical.
+// ---------------------------------------------------------------------------------------------
+namespace mdemi {
+using KernelPairFn = void (*)(GemmParams, GemmParams, int);
+KernelPairFn glds_pair_pick_part0(int al0, int bl0, int al1, int bl1, int v);
+KernelPairFn glds_pair_pick_part1(int al0, int bl0, int al1, int bl1, int v);
+}  // namespace mdemi
+
+enum { PAIR_SEPARATE = 0, PAIR_V11 = 1, PAIR_V8 = 2, PAIR_ARMS = 3 };
+static const int PAIR_ARM_VARIANT[PAIR_ARMS] = {-1, 11, 8};
+static bool g_pair_on = env_on("MDEMI_GEMM_PAIR");
+static bool g_pair_log = env_set("MDEMI_GEMM_PAIR_LOG");
+static int g_pair_force = -1;  // -1: the tuner decides
+static int g_pair_last = -1;   // the arm the last mdemi_gemm_f32_pair call ran
+static std::map<std::pair<TuneKey, TuneKey>, int> g_pair_tuned;
+
+static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+static KernelPairFn pick_pair(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, int v) {
+  if (KernelPairFn f = glds_pair_pick_part0(d0->a_layout, d0->b_layout, d1->a_layout, d1->b_layout, v)) return f;
+  return glds_pair_pick_part1(d0->a_layout, d0->b_layout, d1->a_layout, d1->b_layout, v);
+}
+
+// The two may share a grid at variant v: both run v as itself (dense vectorisable operands,
+// no load-time op), batch 1, a kernel for their layouts, and nothing one writes overlaps
+// anything the other reads or writes.  Anything else is two launches, not an error.
+static bool pair_eligible(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, int v) {
+  if (!pair_variant(v) || d0->batch != 1 || d1->batch != 1) return false;
+  if (!glds_ok(d0) || !glds_ok(d1) || !pick_pair(d0, d1, v)) return false;
+  const size_t ws0 = plan_bytes(d0, plan_for(d0, GEMM_F32, v)), ws1 = plan_bytes(d1, plan_for(d1, GEMM_F32, v));
+  return pair_independent(gemm_footprint(d0, ws0), gemm_footprint(d1, ws1));
+}
+
+static int launch_pair(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, int v, hipStream_t st) {
+  KernelPairFn fn = pick_pair(d0, d1, v);
+  MDEMI_REQUIRE(fn && pair_variant(v), "gemm_pair: no paired kernel for these layouts at variant %d", v);
+  Prepared r0, r1;
+  if (int rc = prepare(d0, v, GEMM_F32, nullptr, r0)) return rc;
+  if (int rc = prepare(d1, v, GEMM_F32, nullptr, r1)) return rc;
+  MDEMI_REQUIRE(r0.g.nblocks + r1.g.nblocks < (int64_t)1 << 31, "gemm_pair: grid too large");
+  if (r0.counters + r1.counters) {  // disjoint ranges of the per-device counters
+    int* cnt = tile_counters(r0.counters + r1.counters, st);
+    if (r0.counters) set_counters(d0, r0, cnt);
+    if (r1.counters) set_counters(d1, r1, cnt ? cnt + r0.counters : nullptr);
+  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)(r0.g.nblocks + r1.g.nblocks)), dim3(GTHREADS), 0, st, r0.p, r1.p,
+                     (int)r0.g.nblocks);
+  if (int rc = finish(d0, r0, st)) return rc;
+  if (int rc = finish(d1, r1, st)) return rc;
+  return check_launch("gemm_f32_pair");
+}
+
+static int run_pair_arm(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, int arm, int v0, int v1, hipStream_t st) {
+  if (arm != PAIR_SEPARATE) return launch_pair(d0, d1, PAIR_ARM_VARIANT[arm], st);
+  if (int rc = launch(d0, v0, st, GEMM_F32)) return rc;
+  return launch(d1, v1, st, GEMM_F32);
+}
+
+static TuneKey tune_key(const mdemi_gemm_desc* d, int mode) {
+  return TuneKey{d->a_layout, d->b_layout, d->a_op, d->b_op, d->M, d->N, d->K, d->batch, d->split_k, mode};
+}
+
+// The arm this pair runs.  Pairing off, a forced arm or a forced variant decide at once; else
+// the cached winner of the two shapes, timed on first use outside a capture (on the unmasked
+// descriptors, as choose_variant does).  An arm the pair is not eligible for is never returned.
+static int choose_pair_arm(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, hipStream_t st) {
+  if (!g_pair_on) return PAIR_SEPARATE;
+  // eligibility (two plans and a footprint comparison per arm) is worked out only for the
+  // arm that would run
+  auto arm_if_ok = [&](int a) {
+    return a != PAIR_SEPARATE && pair_eligible(d0, d1, PAIR_ARM_VARIANT[a]) ? a : (int)PAIR_SEPARATE;
+  };
+  if (g_pair_force >= 0) return arm_if_ok(g_pair_force);
+  if (g_variant >= 0) {
+    for (int a = 1; a < PAIR_ARMS; ++a)
+      if (PAIR_ARM_VARIANT[a] == g_variant) return arm_if_ok(a);
+    return PAIR_SEPARATE;
+  }
+  mdemi_gemm_desc w0 = *d0, w1 = *d1;
+  w0.m_live = w0.k_live = w1.m_live = w1.k_live = nullptr;
+  const std::pair<TuneKey, TuneKey> key{tune_key(&w0, GEMM_F32), tune_key(&w1, GEMM_F32)};
+  {
+    std::lock_guard<std::mutex> lk(g_tune_mu);
+    auto it = g_pair_tuned.find(key);
+    if (it != g_pair_tuned.end()) return arm_if_ok(it->second);
+  }
+  const bool ok[PAIR_ARMS] = {true, pair_eligible(d0, d1, 11), pair_eligible(d0, d1, 8)};
+  // not cached: a pair that cannot share a grid in this call (its pointers, its alignment)
+  // says nothing about the shapes, so nothing is recorded for them
+  if (!ok[PAIR_V11] && !ok[PAIR_V8]) return PAIR_SEPARATE;
+  if (!tunable(&w0, st) || !tunable(&w1, st)) return PAIR_SEPARATE;
+  const int v0 = choose_variant(&w0, st, GEMM_F32), v1 = choose_variant(&w1, st, GEMM_F32);
+  hipEvent_t e0, e1;
+  if (hipEventCreate(&e0) != hipSuccess) return PAIR_SEPARATE;
+  if (hipEventCreate(&e1) != hipSuccess) {
+    (void)hipEventDestroy(e0);
+    return PAIR_SEPARATE;
+  }
+  int best = PAIR_SEPARATE;
+  float best_ms = 1e30f, arm_ms[PAIR_ARMS] = {-1.f, -1.f, -1.f};
+  for (int a = 0; a < PAIR_ARMS; ++a) {
+    if (!ok[a]) continue;
+    if (run_pair_arm(&w0, &w1, a, v0, v1, st) != MDEMI_OK) continue;  // warm (and validate)
+    (void)hipEventRecord(e0, st);
+    for (int r = 0; r < 3; ++r) run_pair_arm(&w0, &w1, a, v0, v1, st);
+    (void)hipEventRecord(e1, st);
+    float ms = 0.f;
+    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) continue;
+    arm_ms[a] = ms / 3.f;
+    if (ms < best_ms) { best_ms = ms; best = a; }  // ties stay two launches
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (g_pair_log)  // MDEMI_GEMM_PAIR_LOG=1: what the tuner measured, once per pair of shapes (ms; -1: arm not run)
+    fprintf(stderr, "mdemi gemm_pair tune: %dx%dx%d/%d (v%d) + %dx%dx%d/%d (v%d): two launches %.4f, pair v11 %.4f, "
+            "pair v8 %.4f -> arm %d\n", w0.M, w0.N, w0.K, w0.split_k, v0, w1.M, w1.N, w1.K, w1.split_k, v1,
+            arm_ms[0], arm_ms[1], arm_ms[2], best);
+  std::lock_guard<std::mutex> lk(g_tune_mu);
+  g_pair_tuned[key] = best;
+  return best;
+}
+
+extern "C" size_t mdemi_gemm_pair_workspace_size(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1) {
+  return align256(mdemi_gemm_workspace_size(d0)) + mdemi_gemm_workspace_size(d1);
+}
+extern "C" size_t mdemi_gemm_pair_workspace_offset(const mdemi_gemm_desc* d0) {
+  return align256(mdemi_gemm_workspace_size(d0));
+}
+
+extern "C" int mdemi_gemm_f32_pair(const mdemi_gemm_desc* d0, const mdemi_gemm_desc* d1, void* stream) {
+  if (int rc = validate(d0)) return rc;
+  if (int rc = validate(d1)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int arm = choose_pair_arm(d0, d1, st);
+  g_pair_last = arm;
+  if (arm != PAIR_SEPARATE) return launch_pair(d0, d1, PAIR_ARM_VARIANT[arm], st);
+  if (int rc = launch(d0, choose_variant(d0, st, GEMM_F32), st, GEMM_F32)) return rc;
+  return launch(d1, choose_variant(d1, st, GEMM_F32), st, GEMM_F32);
+}
+
+extern "C" int mdemi_gemm_pair_set_options(int32_t enabled, int32_t force_arm) {
+  MDEMI_REQUIRE(force_arm >= -1 && force_arm < PAIR_ARMS, "gemm_pair_set_options: bad arm %d", force_arm);
+  g_pair_on = enabled != 0;
+  g_pair_force = force_arm;
+  return MDEMI_OK;
+}
+extern "C" int mdemi_gemm_pair_enabled(void) { return g_pair_on ? 1 : 0; }
+extern "C" int mdemi_gemm_pair_last_arm(void) { return g_pair_last; }
 
 // Benchmark/tuning hooks: force a variant of a family (an index of its table in
 // gemm_plan.h; -1 = per-shape autotune, the default) and the tile raster (group_m > 0:

@@ -285,4 +285,78 @@ MDEMI_HD GemmJob job_of(const G& p, int bid) {
   return j;
 }
 
+// Paired launch (mdemi_gemm_f32_pair): one grid of nblocks0 + nblocks1 workgroups runs two
+// independent GEMMs.  Workgroup `bid` is job `bid` of member 0 when bid < nblocks0, else job
+// bid - nblocks0 of member 1; within a member, job_of maps the job as in its own launch.
+struct PairJob { int member, bid; };
+MDEMI_HD PairJob pair_job_of(int bid, int nblocks0) {
+  return bid < nblocks0 ? PairJob{0, bid} : PairJob{1, bid - nblocks0};
+}
+// the variants a pair can run in one grid: direct-to-LDS, 128x128 tiles
+constexpr bool pair_variant(int v) {
+  return v >= 0 && v < (int)(sizeof(F32_VARIANTS) / sizeof(F32_VARIANTS[0])) && F32_VARIANTS[v].dma &&
+         F32_VARIANTS[v].rows == 128 && F32_VARIANTS[v].cols == 128;
+}
+
+// What a GEMM reads and writes, as byte ranges computed from the descriptor's extents and
+// leading dimensions (batch 1): rows of `width` bytes every `pitch` bytes within [lo, hi)
+// (pitch 0: one row).  Two GEMMs may share a grid only when nothing one writes overlaps
+// anything the other reads or writes.
+struct ByteRange { uintptr_t lo, hi, pitch, width; };
+// Conservative: false only when no byte can be shared -- the spans are apart, or both are
+// rows of one pitch whose column intervals (addresses modulo the pitch) are apart, as
+// column slices of one wider buffer are.
+inline bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+  if (!(a.lo < b.hi && b.lo < a.hi)) return false;
+  const uintptr_t pitch = a.pitch ? a.pitch : b.pitch;
+  if (!pitch || (b.pitch && b.pitch != pitch)) return true;
+  // relative to a's rows, which take residues [0, a.width): b's take [delta, delta + b.width)
+  const uintptr_t delta = b.lo >= a.lo ? (b.lo - a.lo) % pitch : (pitch - (a.lo - b.lo) % pitch) % pitch;
+  return !(delta >= a.width && delta + b.width <= pitch);
+}
+struct GemmFootprint {
+  ByteRange reads[9], writes[4];
+  int nr, nw;
+};
+inline ByteRange span_of(const void* p, int64_t rows, int64_t ld, int64_t cols) {  // rows x cols floats, pitch ld
+  const uintptr_t lo = (uintptr_t)p, w = (uintptr_t)cols * sizeof(float);
+  return ByteRange{lo, lo + (uintptr_t)(rows - 1) * (uintptr_t)ld * sizeof(float) + w,
+                   rows > 1 ? (uintptr_t)ld * sizeof(float) : 0, w};
+}
+// ws_bytes: the bytes of d->workspace the plan uses (0: none)
+inline GemmFootprint gemm_footprint(const mdemi_gemm_desc* d, size_t ws_bytes) {
+  GemmFootprint f{};
+  auto rd = [&](const void* p, int64_t rows, int64_t ld, int64_t cols) {
+    if (p) f.reads[f.nr++] = span_of(p, rows, ld, cols);
+  };
+  auto wr = [&](const void* p, int64_t rows, int64_t ld, int64_t cols) {
+    if (p) f.writes[f.nw++] = span_of(p, rows, ld, cols);
+  };
+  if (d->a_layout == MDEMI_L_KCONTIG) rd(d->A, d->M, d->lda, d->K); else rd(d->A, d->K, d->lda, d->M);
+  if (d->b_layout == MDEMI_L_KCONTIG) rd(d->B, d->N, d->ldb, d->K); else rd(d->B, d->K, d->ldb, d->N);
+  rd(d->aux, d->M, d->ldaux, d->N);
+  rd(d->residual, d->M, d->ldres, d->N);
+  if (d->bias_mode != MDEMI_BIAS_NONE) rd(d->bias, 1, 0, d->bias_mode == MDEMI_BIAS_ROW ? d->M : d->N);
+  if (d->row_scale) rd(d->row_scale, 1, 0, ceil_div(d->M, d->row_scale_group));
+  if (d->m_live) rd(d->m_live, 1, 0, ceil_div(d->M, d->m_live_group));
+  if (d->k_live) rd(d->k_live, 1, 0, ceil_div(d->K, d->k_live_group));
+  wr(d->C, d->M, d->ldc, d->N);
+  wr(d->preact, d->M, d->ldpre, d->N);
+  wr(d->rowsum_a, 1, 0, d->M);
+  if (ws_bytes && d->workspace) f.writes[f.nw++] = ByteRange{(uintptr_t)d->workspace, (uintptr_t)d->workspace + ws_bytes, 0, ws_bytes};
+  return f;
+}
+inline bool pair_independent(const GemmFootprint& f0, const GemmFootprint& f1) {
+  auto clash = [](const GemmFootprint& w, const GemmFootprint& o) {
+    for (int i = 0; i < w.nw; ++i) {
+      for (int j = 0; j < o.nr; ++j)
+        if (ranges_overlap(w.writes[i], o.reads[j])) return true;
+      for (int j = 0; j < o.nw; ++j)
+        if (ranges_overlap(w.writes[i], o.writes[j])) return true;
+    }
+    return false;
+  };
+  return !clash(f0, f1) && !clash(f1, f0);
+}
+
 }  // namespace mdemi

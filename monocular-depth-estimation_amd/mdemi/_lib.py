@@ -154,6 +154,12 @@ _SIGS = {
                                           vp, vp]),
     "mdemi_chan_scale16": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i64, i32, vp]),
     "mdemi_gemm_set_options": (ctypes.c_int, [i32, i32]),
+    "mdemi_gemm_f32_pair": (ctypes.c_int, [ctypes.POINTER(GemmDesc), ctypes.POINTER(GemmDesc), vp]),
+    "mdemi_gemm_pair_workspace_size": (sz, [ctypes.POINTER(GemmDesc), ctypes.POINTER(GemmDesc)]),
+    "mdemi_gemm_pair_workspace_offset": (sz, [ctypes.POINTER(GemmDesc)]),
+    "mdemi_gemm_pair_set_options": (ctypes.c_int, [i32, i32]),
+    "mdemi_gemm_pair_enabled": (ctypes.c_int, []),
+    "mdemi_gemm_pair_last_arm": (ctypes.c_int, []),
     "mdemi_colsum_workspace_size": (sz, [i64, i64]),
     "mdemi_colsum_f32": (ctypes.c_int, [vp, i64, i64, i64, vp, ctypes.c_int, vp, vp]),
     "mdemi_headconv_fwd": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -295,32 +295,13 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_layout, b_layout, a_op=L.OP_NONE,
                  a_bstride=a_bstride, b_bstride=b_bstride, c_bstride=c_bstride, split_k=split_k, conv=conv,
                  a_off=a_off + i * a2, b_off=b_off + i * b2, c_off=c_off + i * c2)
         return C
-    d = L.GemmDesc()
-    d.M, d.N, d.K, d.batch = M, N, K, batch
-    if inner is not None and inner[0] > 1:
-        d.batch_inner, d.a_bstride_inner, d.b_bstride_inner, d.c_bstride_inner = inner
-    d.A = A.data_ptr() + 4 * a_off if A is not None else None
-    d.B = B.data_ptr() + 4 * b_off if B is not None else None
-    d.lda, d.a_bstride, d.a_layout, d.a_op = lda, a_bstride, a_layout, a_op
-    d.ldb, d.b_bstride, d.b_layout, d.b_op = ldb, b_bstride, b_layout, b_op
-    d.C, d.ldc, d.c_bstride = C.data_ptr() + 4 * c_off, ldc, c_bstride
-    d.alpha, d.beta = alpha, beta
-    d.bias, d.bias_mode, d.act = (bias.data_ptr() if bias is not None else None), bias_mode, act
-    d.aux, d.ldaux, d.aux_bstride = (aux.data_ptr() if aux is not None else None), ldaux, aux_bstride
-    d.residual, d.ldres, d.res_bstride = (residual.data_ptr() if residual is not None else None), ldres, res_bstride
-    d.split_k = split_k if split_k is not None else _split_for(M, N, K)
-    if conv is not None:
-        d.conv = conv
-    if preact is not None:
-        d.preact, d.ldpre, d.pre_bstride = preact.data_ptr(), ldpre, pre_bstride
-    if rowsum_a is not None:
-        d.rowsum_a = rowsum_a.data_ptr()
-    if row_scale is not None:
-        d.row_scale, d.row_scale_group = row_scale.data_ptr(), row_scale_group
-    if m_live is not None:
-        d.m_live, d.m_live_group = m_live.data_ptr(), M // m_live.numel()
-    if k_live is not None:
-        d.k_live, d.k_live_group = k_live.data_ptr(), K // k_live.numel()
+    d = _gemm_desc(A, B, C, M, N, K, lda=lda, ldb=ldb, ldc=ldc, a_layout=a_layout, b_layout=b_layout, a_op=a_op,
+                   b_op=b_op, alpha=alpha, beta=beta, bias=bias, bias_mode=bias_mode, act=act, aux=aux, ldaux=ldaux,
+                   residual=residual, ldres=ldres, batch=batch, a_bstride=a_bstride, b_bstride=b_bstride,
+                   c_bstride=c_bstride, aux_bstride=aux_bstride, res_bstride=res_bstride, split_k=split_k, conv=conv,
+                   preact=preact, ldpre=ldpre, pre_bstride=pre_bstride, rowsum_a=rowsum_a, a_off=a_off, b_off=b_off,
+                   c_off=c_off, inner=inner, row_scale=row_scale, row_scale_group=row_scale_group, m_live=m_live,
+                   k_live=k_live)
     lib = L.load()
     need = lib.mdemi_gemm_workspace_size(ctypes.byref(d))
     if need:
@@ -363,6 +344,88 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_layout, b_layout, a_op=L.OP_NONE,
     else:
         L.check(lib.mdemi_gemm_f32(ctypes.byref(d), L.stream()), "gemm_f32")
     return C
+
+
+def _gemm_desc(A, B, C, M, N, K, *, lda, ldb, ldc, a_layout, b_layout, a_op=L.OP_NONE, b_op=L.OP_NONE,
+               alpha=1.0, beta=0.0, bias=None, bias_mode=L.BIAS_NONE, act=L.ACT_NONE, aux=None, ldaux=0,
+               residual=None, ldres=0, batch=1, a_bstride=0, b_bstride=0, c_bstride=0, aux_bstride=0,
+               res_bstride=0, split_k=None, conv=None, preact=None, ldpre=0, pre_bstride=0, rowsum_a=None,
+               a_off=0, b_off=0, c_off=0, inner=None, row_scale=None, row_scale_group=0, m_live=None, k_live=None):
+    """The mdemi_gemm_desc of one gemm() call (its arguments; no workspace yet)."""
+    d = L.GemmDesc()
+    d.M, d.N, d.K, d.batch = M, N, K, batch
+    if inner is not None and inner[0] > 1:
+        d.batch_inner, d.a_bstride_inner, d.b_bstride_inner, d.c_bstride_inner = inner
+    d.A = A.data_ptr() + 4 * a_off if A is not None else None
+    d.B = B.data_ptr() + 4 * b_off if B is not None else None
+    d.lda, d.a_bstride, d.a_layout, d.a_op = lda, a_bstride, a_layout, a_op
+    d.ldb, d.b_bstride, d.b_layout, d.b_op = ldb, b_bstride, b_layout, b_op
+    d.C, d.ldc, d.c_bstride = C.data_ptr() + 4 * c_off, ldc, c_bstride
+    d.alpha, d.beta = alpha, beta
+    d.bias, d.bias_mode, d.act = (bias.data_ptr() if bias is not None else None), bias_mode, act
+    d.aux, d.ldaux, d.aux_bstride = (aux.data_ptr() if aux is not None else None), ldaux, aux_bstride
+    d.residual, d.ldres, d.res_bstride = (residual.data_ptr() if residual is not None else None), ldres, res_bstride
+    d.split_k = split_k if split_k is not None else _split_for(M, N, K)
+    if conv is not None:
+        d.conv = conv
+    if preact is not None:
+        d.preact, d.ldpre, d.pre_bstride = preact.data_ptr(), ldpre, pre_bstride
+    if rowsum_a is not None:
+        d.rowsum_a = rowsum_a.data_ptr()
+    if row_scale is not None:
+        d.row_scale, d.row_scale_group = row_scale.data_ptr(), row_scale_group
+    if m_live is not None:
+        d.m_live, d.m_live_group = m_live.data_ptr(), M // m_live.numel()
+    if k_live is not None:
+        d.k_live, d.k_live_group = k_live.data_ptr(), K // k_live.numel()
+    return d
+
+
+def _pair_native(kw0, kw1):
+    """gemm_pair takes the library's paired entry: fp32 precision, pairing on, a library that
+    has the entry, and gemm() itself in place -- a caller that wraps functional.gemm (the
+    benchmark's roofline step, tools/gemm_shapes.py) must keep seeing every GEMM."""
+    if _PRECISION[0] != "fp32" or globals()["gemm"] is not _GEMM:
+        return False
+    for kw in (kw0, kw1):
+        if any(kw.get(k) is not None for k in ("a16", "b16", "c16", "inner")):
+            return False
+    lib = L.load()
+    if getattr(lib, "mdemi_gemm_f32_pair", None) is None:  # an A/B build of an older ABI (MDEMI_LIB)
+        return False
+    return lib.mdemi_gemm_pair_enabled() != 0
+
+
+_GEMM = gemm  # gemm() as defined here: gemm_pair pairs only while functional.gemm is still this
+
+
+def gemm_pair(kw0, kw1):
+    """Two gemm() calls given as their keyword dicts (A, B, C, M, N, K and the rest), with the
+    effect of gemm(**kw0) then gemm(**kw1), bit for bit.  In fp32 precision the library runs
+    two independent GEMMs of the direct-to-LDS 128x128 variants as one launch where that is
+    faster (mdemi_gemm_f32_pair: an input gradient beside a weight gradient); everything else,
+    and every other precision, is the two calls."""
+    if not _pair_native(kw0, kw1):
+        g = globals()["gemm"]  # the module's current gemm: a wrapper sees both calls
+        for kw in (kw0, kw1):
+            rest = {k: v for k, v in kw.items() if k not in ("A", "B", "C", "M", "N", "K")}
+            g(kw["A"], kw["B"], kw["C"], kw["M"], kw["N"], kw["K"], **rest)
+        return
+    strip = ("a16", "b16", "c16")
+    d0 = _gemm_desc(**{k: v for k, v in kw0.items() if k not in strip})
+    d1 = _gemm_desc(**{k: v for k, v in kw1.items() if k not in strip})
+    lib = L.load()
+    need = lib.mdemi_gemm_pair_workspace_size(ctypes.byref(d0), ctypes.byref(d1))
+    if need:
+        # one buffer for both members (GEMMs are stream-ordered, so no other GEMM's slabs are live)
+        ws = L.workspace(need, kw0["C"].device, slot=1)
+        off = lib.mdemi_gemm_pair_workspace_offset(ctypes.byref(d0))
+        if off:
+            d0.workspace, d0.workspace_bytes = ws.data_ptr(), off
+        if need > off:
+            d1.workspace, d1.workspace_bytes = ws.data_ptr() + off, ws.numel() - off
+    LAST_GEMM[0] = "fp32"
+    L.check(lib.mdemi_gemm_f32_pair(ctypes.byref(d0), ctypes.byref(d1), L.stream()), "gemm_f32_pair")
 
 
 class B16Unsupported(RuntimeError):
@@ -464,25 +527,36 @@ class _LinearFn(torch.autograd.Function):
         if ctx.drop_scale is not None:  # the branch's gradient; the residual's stays dy
             dy2 = _drop_rows(dy2, ctx.drop_scale)
         dx = dw = db = None
+        kw_dx = kw_dw = dx16 = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, device=dy.device, dtype=torch.float32)
             dx16 = new_b16_like(dx) if ctx.dx16 else None  # dX is the next GEMM backward's operand
             # dX[M,K] = dY[M,N] . W[N,K]  (times gelu'(h) when the forward read gelu(h))
-            gemm(dy2, weight, dx, M, K, N, lda=N, ldb=K, ldc=K, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG,
-                 act=L.ACT_GELU_GRAD if ctx.in_gelu else L.ACT_NONE, aux=x2 if ctx.in_gelu else None,
-                 ldaux=K, c16=dx16, m_live=ctx.live)
-            if dx16 is not None:
-                set_b16(dx, dx16)
-            dx = dx.view(ctx.xshape)
+            kw_dx = dict(A=dy2, B=weight, C=dx, M=M, N=K, K=N, lda=N, ldb=K, ldc=K, a_layout=L.L_KCONTIG,
+                         b_layout=L.L_MNCONTIG, act=L.ACT_GELU_GRAD if ctx.in_gelu else L.ACT_NONE,
+                         aux=x2 if ctx.in_gelu else None, ldaux=K, c16=dx16, m_live=ctx.live)
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
         if want_db:
             db = torch.empty(N, device=dy.device, dtype=torch.float32)
         if ctx.needs_input_grad[1]:
             dw = torch.empty(N, K, device=dy.device, dtype=torch.float32)
             # dW[N,K] = dY^T . X  (reduction over the M rows; split-K slabs); db = dY^T 1 rides along
-            gemm(dy2, x2, dw, N, K, M, lda=N, ldb=K, ldc=K, a_layout=L.L_MNCONTIG, b_layout=L.L_MNCONTIG,
-                 b_op=L.OP_GELU if ctx.in_gelu else L.OP_NONE, rowsum_a=db, k_live=ctx.live)
-        elif want_db:
+            kw_dw = dict(A=dy2, B=x2, C=dw, M=N, N=K, K=M, lda=N, ldb=K, ldc=K, a_layout=L.L_MNCONTIG,
+                         b_layout=L.L_MNCONTIG, b_op=L.OP_GELU if ctx.in_gelu else L.OP_NONE, rowsum_a=db,
+                         k_live=ctx.live)
+        if kw_dx is not None and kw_dw is not None:
+            # both read dy2 and write apart: one launch where that is faster, the weight
+            # gradient's long-K pieces first so the tail is made of short jobs
+            gemm_pair(kw_dw, kw_dx)
+        elif kw_dx is not None:
+            gemm(**kw_dx)
+        elif kw_dw is not None:
+            gemm(**kw_dw)
+        if dx is not None:
+            if dx16 is not None:
+                set_b16(dx, dx16)
+            dx = dx.view(ctx.xshape)
+        if kw_dw is None and want_db:
             colsum(dy2, out=db)
         dres = dy if ctx.has_res and ctx.needs_input_grad[3] else None
         return dx, dw, db, dres, None, None, None, None
@@ -575,31 +649,37 @@ class _MlpFn(torch.autograd.Function):
         dw2 = torch.empty(N, Hd, device=dev, dtype=torch.float32)
         db2 = torch.empty(N, device=dev, dtype=torch.float32) if has_b2 else None
         # with `live`, d2 = 0 * dy on the dead samples' rows, so dh below is zero there too
-        gemm(d2, g, dw2, N, Hd, M, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_MNCONTIG, b_layout=L.L_MNCONTIG,
-             rowsum_a=db2, k_live=live)
+        kw_dw2 = dict(A=d2, B=g, C=dw2, M=N, N=Hd, K=M, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_MNCONTIG,
+                      b_layout=L.L_MNCONTIG, rowsum_a=db2, k_live=live)
         dh = torch.empty(M, Hd, device=dev, dtype=torch.float32)
         if p_mid > 0.0:
+            gemm(**kw_dw2)
             gemm(d2, w2, dh, M, Hd, N, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG)
             _drop(dh.data_ptr(), dh.data_ptr(), dh.numel(), p_mid, seed)
             L.call("mdemi_elementwise", L.EW_ACT_BWD, h.data_ptr(), dh.data_ptr(), dh.data_ptr(), dh.numel(),
                    float(act), 0.0, L.stream())
         else:
             dh16 = new_b16_like(dh)  # the operand of both fc1 gradient GEMMs
-            gemm(d2, w2, dh, M, Hd, N, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG,
-                 act=L.ACT_GRAD_OF[act], aux=h, ldaux=Hd, c16=dh16, m_live=live)
+            # the two fc2 gradients read d2 and write apart: one launch where that is faster,
+            # the weight gradient's long-K pieces first so the tail is made of short jobs
+            gemm_pair(kw_dw2, dict(A=d2, B=w2, C=dh, M=M, N=Hd, K=N, lda=N, ldb=Hd, ldc=Hd, a_layout=L.L_KCONTIG,
+                                   b_layout=L.L_MNCONTIG, act=L.ACT_GRAD_OF[act], aux=h, ldaux=Hd, c16=dh16,
+                                   m_live=live))
             if dh16 is not None:
                 set_b16(dh, dh16)
         del h, g
         dw1 = torch.empty(Hd, K, device=dev, dtype=torch.float32)
         db1 = torch.empty(Hd, device=dev, dtype=torch.float32) if has_b1 else None
-        gemm(dh, x2, dw1, Hd, K, M, lda=Hd, ldb=K, ldc=K, a_layout=L.L_MNCONTIG, b_layout=L.L_MNCONTIG,
-             rowsum_a=db1, k_live=live)
+        kw_dw1 = dict(A=dh, B=x2, C=dw1, M=Hd, N=K, K=M, lda=Hd, ldb=K, ldc=K, a_layout=L.L_MNCONTIG,
+                      b_layout=L.L_MNCONTIG, rowsum_a=db1, k_live=live)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(M, K, device=dev, dtype=torch.float32)
-            gemm(dh, w1, dx, M, K, Hd, lda=Hd, ldb=K, ldc=K, a_layout=L.L_KCONTIG, b_layout=L.L_MNCONTIG,
-                 m_live=live)
+            gemm_pair(kw_dw1, dict(A=dh, B=w1, C=dx, M=M, N=K, K=Hd, lda=Hd, ldb=K, ldc=K, a_layout=L.L_KCONTIG,
+                                   b_layout=L.L_MNCONTIG, m_live=live))
             dx = dx.view(ctx.xshape)
+        else:
+            gemm(**kw_dw1)
         dres = dy if has_res and ctx.needs_input_grad[5] else None
         return dx, dw1, db1, dw2, db2, dres, None
 

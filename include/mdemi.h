@@ -310,6 +310,9 @@ int mdemi_layernorm_bwd_add(const float* dy, const float* x, const float* mean,
 /* q,k,v,out, dq,dk,dv are token-major rows of the UNPADDED [B,H,W] grid.    */
 /* Pad tokens take the value of *_pad (the Linear's bias, because the        */
 /* reference pads after norm1 so pad rows of qkv(0) == bias) or 0 if NULL.   */
+/* q, k, v each own heads * head_dim columns from their pointer on; q and k  */
+/* share qk_ld, and the leading dimensions may exceed the owned width        */
+/* (columns past it, and rows past B*H*W, are neither read nor written).     */
 /* ------------------------------------------------------------------------ */
 typedef struct mdemi_winattn_desc {
   int32_t B, H, W, heads, head_dim, window, shift, _pad0;
@@ -320,14 +323,20 @@ typedef struct mdemi_winattn_desc {
   const float* v; int64_t v_ld; const float* v_pad;
   const float* rpb_table;          /* [(2w-1)^2][heads] */
   float* out; int64_t out_ld;     /* forward output; the backward reads it (D = rowsum(dO*O)) */
-  float* lse;                      /* [nwin][heads][window^2] row log-sum-exp: written by the
-                                      forward (may be NULL there), required by the backward */
+  float* lse;                      /* [nwin][heads][window^2] row log-sum-exp, nwin = B * ceil(H/w) *
+                                      ceil(W/w) windows ordered (b, wy, wx), the window's tokens
+                                      row-major; +inf for a pad query.  Written by the forward (may
+                                      be NULL there: out is the same), required by the backward */
   /* backward only */
-  const float* dout;
-  float* dq; float* dk; int64_t dqk_ld;
-  float* dv; int64_t dv_ld;
-  float* d_rpb_table;              /* [(2w-1)^2][heads], overwritten */
-  float* dq_pad; float* dk_pad; float* dv_pad;   /* [C] sums over pad tokens, overwritten (may be NULL) */
+  const float* dout;               /* rows laid out like out: leading dimension out_ld */
+  float* dq; float* dk; int64_t dqk_ld;   /* may differ from qk_ld */
+  float* dv; int64_t dv_ld;               /* may differ from v_ld */
+  float* d_rpb_table;              /* [(2w-1)^2][heads], overwritten in full */
+  float* dq_pad; float* dk_pad; float* dv_pad;   /* [heads * head_dim] sums over pad tokens, each
+                                      overwritten in full; dq_pad with zeros (a pad query's row
+                                      is cropped away, so it receives no gradient).  Each may be
+                                      NULL, which suppresses that vector alone: every other
+                                      output is written as before */
   void* workspace; int64_t workspace_bytes;
   const float* sample_live;        /* optional [B], read on the device only: a sample whose entry
                                       == 0.0f is dead (DropPath dropped its branch).  The forward

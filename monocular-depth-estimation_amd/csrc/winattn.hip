@@ -198,17 +198,17 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The wave's (window, head) item.  The last workgroup may hold waves past the last item: the
+// kernels return on `item >= nitems` before they touch global memory -- wave-uniform, and safe
+// because the waves of a workgroup meet at no workgroup barrier (wave_lds_sync above).
 struct WaItem {
   int item, win, hh;
-  bool active;
 };
-__device__ __forceinline__ WaItem wa_item(const WinParams& p, int nitems) {
+__device__ __forceinline__ WaItem wa_item(const WinParams& p) {
   WaItem it;
   it.item = blockIdx.x * WA_WAVES + (threadIdx.x >> 6);
-  it.active = it.item < nitems;
-  const int i = it.active ? it.item : 0;
-  it.win = i / p.g.heads;
-  it.hh = i % p.g.heads;
+  it.win = it.item / p.g.heads;
+  it.hh = it.item % p.g.heads;
   return it;
 }
 
@@ -216,9 +216,7 @@ __device__ __forceinline__ WaItem wa_item(const WinParams& p, int nitems) {
 // Wave-uniform -- a wave owns one (window, head) and a window lies in one sample -- and the
 // waves of a workgroup meet at no workgroup barrier (wave_lds_sync above), so a dead wave
 // writes its zeros and returns while its neighbours run on.
-__device__ __forceinline__ bool wa_dead(const WinParams& p, const WaItem& it, int b) {
-  return p.live && it.active && p.live[b] == 0.f;
-}
+__device__ __forceinline__ bool wa_dead(const WinParams& p, int b) { return p.live && p.live[b] == 0.f; }
 // zeros to columns [col0, col0 + WA_HD) of the rows of the window's real tokens
 __device__ __forceinline__ void wa_zero_rows(const WinGeom& g, const Win<7>& w, float* base, int64_t ld, int col0,
                                              int lane) {
@@ -243,10 +241,11 @@ __global__ __launch_bounds__(256) void winattn_fwd_kernel(WinParams p, const flo
   __shared__ int8_t regs[WA_WAVES][WA_NP];
   const WinGeom& g = p.g;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
-  const WaItem it = wa_item(p, nitems);
+  const WaItem it = wa_item(p);
+  if (it.item >= nitems) return;
   const Win<WS> w(g, it.win);
   const int col0 = it.hh * HD;
-  if (wa_dead(p, it, w.b)) {
+  if (wa_dead(p, w.b)) {
     wa_zero_rows(g, w, p.out, p.out_ld, col0, lane);
     if (p.lse && lane < WA_N) p.lse[(int64_t)it.item * WA_N + lane] = 0.f;
     return;
@@ -316,7 +315,6 @@ __global__ __launch_bounds__(256) void winattn_fwd_kernel(WinParams p, const flo
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[n][r] = 0.f;
   mma_tok(o, Vs[wv], s, l31, h);  // O^T[d][q] = sum_key V[key][d] P^T[key][q]
-  if (!it.active) return;
 #pragma unroll
   for (int n = 0; n < 2; ++n) {
     const int q = n * 32 + l31;
@@ -434,10 +432,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WA_BWD_OCC,
   __shared__ int rowtab[WA_WAVES][WA_NP];
   const WinGeom& g = p.g;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l31 = lane & 31, h = lane >> 5;
-  const WaItem it = wa_item(p, nitems);
+  const WaItem it = wa_item(p);
+  if (it.item >= nitems) return;
   const Win<WS> w(g, it.win);
   const int col0 = it.hh * HD;
-  if (wa_dead(p, it, w.b)) {  // what a zero dout gives: zero dq / dk / dv rows, zero partials
+  if (wa_dead(p, w.b)) {  // what a zero dout gives: zero dq / dk / dv rows, zero partials
     wa_zero_rows(g, w, p.dq, p.dqk_ld, col0, lane);
     wa_zero_rows(g, w, p.dk, p.dqk_ld, col0, lane);
     wa_zero_rows(g, w, p.dv, p.dv_ld, col0, lane);
@@ -518,7 +517,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WA_BWD_OCC,
     for (int j = 0; j < 25; ++j)
 #pragma unroll
       for (int ti = 0; ti < 2; ++ti) acc[ti] = mfma32(tbuf[wv][ti * 32 + l31][2 * j + h], colv[j], acc[ti]);
-    if (!it.active) return;
     if (fast) {
       float* gb = gbase + col0 + l31;
       const int* rt = rowtab[wv];
@@ -615,17 +613,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WA_BWD_OCC,
 #pragma unroll
         for (int n = 0; n < 2; ++n)
           dq[n] = mfma32(kc[t][r], tbuf[wv][t * 32 + acc_row(r, h)][n * 32 + l31], dq[n]);
-    if (it.active) {
 #pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        if (!treal[n] || trow[n] < 0) continue;  // padding / pad query: cropped away
-        float* dst = p.dq + (int64_t)trow[n] * p.dqk_ld + col0;
+    for (int n = 0; n < 2; ++n) {
+      if (!treal[n] || trow[n] < 0) continue;  // padding / pad query: cropped away
+      float* dst = p.dq + (int64_t)trow[n] * p.dqk_ld + col0;
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
-          *reinterpret_cast<float4*>(dst + 8 * a + 4 * h) =
-              make_float4(dq[n][4 * a] * p.scale, dq[n][4 * a + 1] * p.scale, dq[n][4 * a + 2] * p.scale,
-                          dq[n][4 * a + 3] * p.scale);
-      }
+      for (int a = 0; a < 4; ++a)
+        *reinterpret_cast<float4*>(dst + 8 * a + 4 * h) =
+            make_float4(dq[n][4 * a] * p.scale, dq[n][4 * a + 1] * p.scale, dq[n][4 * a + 2] * p.scale,
+                        dq[n][4 * a + 3] * p.scale);
     }
   }
   // dK[key][d] = sum_q dS^T[key][q] (scale Q)[q][d]
@@ -654,19 +650,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WA_BWD_OCC,
     for (int e = 0; e < ND; ++e) Eb[lane * ND + e] = E[e];
   }
   wave_lds_sync();  // E, pads complete
-  if (it.active) {
-    float* P = p.partial + (int64_t)it.item * (WA_T + 2 * HD);
-    for (int e = lane; e < WA_T; e += 64) {
-      const int dy = e / ND - (WS - 1), dxi = e % ND;
-      const int ky0 = max(0, -dy), ky1 = min(WS - 1, WS - 1 - dy);
-      float acc = 0.f;
-      for (int ky = ky0; ky <= ky1; ++ky) acc += Eb[(ky * WS + ky + dy) * ND + dxi];
-      P[e] = acc;
-    }
-    if (lane < HD) {
-      P[WA_T + lane] = padk[wv][lane];
-      P[WA_T + HD + lane] = padv[wv][lane];
-    }
+  float* P = p.partial + (int64_t)it.item * (WA_T + 2 * HD);
+  for (int e = lane; e < WA_T; e += 64) {
+    const int dy = e / ND - (WS - 1), dxi = e % ND;
+    const int ky0 = max(0, -dy), ky1 = min(WS - 1, WS - 1 - dy);
+    float acc = 0.f;
+    for (int ky = ky0; ky <= ky1; ++ky) acc += Eb[(ky * WS + ky + dy) * ND + dxi];
+    P[e] = acc;
+  }
+  if (lane < HD) {
+    P[WA_T + lane] = padk[wv][lane];
+    P[WA_T + HD + lane] = padv[wv][lane];
   }
 }
 

@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from gemm_plan_util import tail_plan_m_split as _tail_plan_m_split
+from winattn_contract_ref import _ref_window_attn
 
 pytestmark = pytest.mark.gpu
 
@@ -137,56 +138,6 @@ def test_layernorm(mf, rows, C):
     close(xg.grad, xr.grad, rtol=1e-4)
     close(gg.grad, gr.grad, rtol=1e-4)
     close(bg.grad, br.grad, rtol=1e-4)
-
-
-def _ref_window_attn(qk, qk_bias, v, v_bias, rpb, B, H, W, heads, ws, shift, scale, C, v_off):
-    """Direct restatement of WindowAttention + pad/roll/partition (swin_transformer.py:112-240)."""
-    hd = C // heads
-    rows = B * H * W
-    q = qk[:, :C]
-    k = qk[:, C:2 * C]
-    vv = v[:, v_off:v_off + C]
-    Hp, Wp = -(-H // ws) * ws, -(-W // ws) * ws
-
-    def grid(t, pad):
-        t = t.view(B, H, W, C)
-        full = (pad.view(1, 1, 1, C) if pad is not None else torch.zeros(1, 1, 1, C, dtype=t.dtype)).expand(
-            B, Hp, Wp, C).clone()
-        full[:, :H, :W] = t
-        if shift:
-            full = torch.roll(full, (-shift, -shift), (1, 2))
-        return full.view(B, Hp // ws, ws, Wp // ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws, C)
-
-    qw = grid(q, qk_bias[:C] if qk_bias is not None else None)
-    kw = grid(k, qk_bias[C:2 * C] if qk_bias is not None else None)
-    vw = grid(vv, v_bias[v_off:v_off + C] if v_bias is not None else None)
-    nW = qw.shape[0] // B
-    qh = qw.view(-1, ws * ws, heads, hd).transpose(1, 2) * scale
-    kh = kw.view(-1, ws * ws, heads, hd).transpose(1, 2)
-    vh = vw.view(-1, ws * ws, heads, hd).transpose(1, 2)
-    attn = qh @ kh.transpose(-2, -1)
-    coords = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
-    rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0)
-    idx = (rel[..., 0] + ws - 1) * (2 * ws - 1) + rel[..., 1] + ws - 1
-    attn = attn + rpb[idx.view(-1)].view(ws * ws, ws * ws, heads).permute(2, 0, 1).unsqueeze(0)
-    if shift:
-        img = torch.zeros(1, Hp, Wp, 1, dtype=qk.dtype)
-        cnt = 0
-        for hs in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
-            for wsl in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
-                img[:, hs, wsl, :] = cnt
-                cnt += 1
-        mw = img.view(1, Hp // ws, ws, Wp // ws, ws, 1).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws * ws)
-        mask = mw.unsqueeze(1) - mw.unsqueeze(2)
-        mask = mask.masked_fill(mask != 0, -100.0).masked_fill(mask == 0, 0.0)
-        attn = attn.view(B, nW, heads, ws * ws, ws * ws) + mask.unsqueeze(1).unsqueeze(0)
-        attn = attn.view(-1, heads, ws * ws, ws * ws)
-    attn = attn.softmax(-1)
-    o = (attn @ vh).transpose(1, 2).reshape(-1, ws * ws, C)
-    o = o.view(B, Hp // ws, Wp // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, Hp, Wp, C)
-    if shift:
-        o = torch.roll(o, (shift, shift), (1, 2))
-    return o[:, :H, :W].reshape(rows, C)
 
 
 @pytest.mark.parametrize("H,W,shift,swin", [(14, 14, 0, True), (10, 12, 3, True), (9, 16, 3, False),

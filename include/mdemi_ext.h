@@ -172,6 +172,41 @@ int mdemi_depth_metrics(const float* pred, const float* gt, int32_t B, int32_t H
                         double* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Scale- and shift-aligned metrics (cfg eval.align; this framework's own    */
+/* definition).  Per image, over the same valid set V (n       */
+/* pixels, p the unclamped prediction, g the ground truth):                  */
+/*   MEDIAN      s = median(g) / median(p), t = 0; numpy's median (even n:   */
+/*               the mean of the two middle order statistics), the order     */
+/*               statistics exact on the fp32 values, mean and quotient fp64 */
+/*   LSTSQ       (s, t) minimise sum (s p + t - g)^2, every sum in fp64:     */
+/*               det = n Spp - Sp^2, s = (n Spg - Sp Sg) / det,              */
+/*               t = (Spp Sg - Sp Spg) / det                                 */
+/*   LSTSQ_DISP  the same solve on x = 1/p, y = 1/g (fp64 reciprocals)       */
+/* An image fails (status 1, s = 1, t = 0, evaluated unaligned) when n == 0, */
+/* median(p) is not > 0 or det is not finite and > 0.                        */
+/* mdemi_depth_align writes coef [B][4] = s, t, n, status (fp64).  It does   */
+/* not synchronise or allocate; the workspace is cleared on the stream.      */
+/* mdemi_depth_metrics_aligned reads coef on the device, forms               */
+/*   q = (float)(s p + t)            (MEDIAN, LSTSQ)                         */
+/*   q = (float)(1 / max(s / p + t, 1 / max_depth))   (LSTSQ_DISP)           */
+/* in fp64 rounded once (q = p on a failed image), writes it to aligned      */
+/* [B][H][W] on every pixel when that is not NULL, and reduces the metrics   */
+/* of q exactly as mdemi_depth_metrics would (same bits): out [B][12] = its  */
+/* ten columns, then s and t.  workspace: mdemi_depth_metrics_workspace_size.*/
+/* ------------------------------------------------------------------------ */
+#define MDEMI_ALIGN_MEDIAN 1
+#define MDEMI_ALIGN_LSTSQ 2
+#define MDEMI_ALIGN_LSTSQ_DISP 3
+size_t mdemi_depth_align_workspace_size(int32_t B, int32_t H, int32_t W, int32_t mode);
+int mdemi_depth_align(const float* pred, const float* gt, int32_t B, int32_t H, int32_t W, int32_t y0, int32_t y1,
+                      int32_t x0, int32_t x1, float min_depth, float max_depth, int32_t mode, double* coef,
+                      void* workspace, void* stream);
+int mdemi_depth_metrics_aligned(const float* pred, const float* gt, int32_t B, int32_t H, int32_t W, int32_t y0,
+                                int32_t y1, int32_t x0, int32_t x1, float min_depth, float max_depth,
+                                int32_t clamp_pred, int32_t mode, const double* coef, float* aligned, double* out,
+                                void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Flip-eval (config eval.flip_eval): rows of W floats (an NCHW batch is     */
 /* B*C*H rows).  flip_w: y[r][w] = x[r][W-1-w] (out of place).              */
 /* flip_avg_w: y[r][w] = (a[r][w] + b[r][W-1-w]) / 2; y may alias a.        */

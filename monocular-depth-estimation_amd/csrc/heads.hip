@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include "mdemi_ext.h"
+#include "metrics_kernel.h"
 
 namespace mdemi {
 
@@ -530,86 +531,6 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict
   }
 }
 
-// ---------------------------------------------------------------------------
-// depth metrics: grid (chunks, B); 11 sums per image
-// ---------------------------------------------------------------------------
-constexpr int MET_N = 11;  // count, a1, a2, a3, abs_rel, sq_rel, sq, sq_log, err, err^2, log10
-
-__global__ __launch_bounds__(256) void metrics_partial(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                       double* __restrict__ part, int H, int W, int y0, int y1, int x0,
-                                                       int x1, float dmin, float dmax, int clamp_pred, int nchunk) {
-  __shared__ float red[MET_N][4];
-  const int b = blockIdx.y, ch = blockIdx.x;
-  const int64_t HW = (int64_t)H * W;
-  const int64_t per = (HW + nchunk - 1) / nchunk;
-  const int64_t p0 = (int64_t)ch * per, p1 = min(HW, p0 + per);
-  float acc[MET_N];
-#pragma unroll
-  for (int i = 0; i < MET_N; ++i) acc[i] = 0.f;
-  for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-    const int y = (int)(p / W), x = (int)(p % W);
-    const float g = gt[(int64_t)b * HW + p];
-    if (y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax)) continue;
-    float q = pred[(int64_t)b * HW + p];
-    if (clamp_pred) q = fminf(fmaxf(q, dmin), dmax);
-    const float th = fmaxf(g / q, q / g);
-    const float diff = g - q;
-    const float lg = logf(g), lq = logf(q);
-    const float err = lq - lg;
-    acc[0] += 1.f;
-    acc[1] += th < 1.25f ? 1.f : 0.f;
-    acc[2] += th < 1.25f * 1.25f ? 1.f : 0.f;
-    acc[3] += th < 1.25f * 1.25f * 1.25f ? 1.f : 0.f;
-    acc[4] += fabsf(diff) / g;
-    acc[5] += diff * diff / g;
-    acc[6] += diff * diff;
-    acc[7] += (lg - lq) * (lg - lq);
-    acc[8] += err;
-    acc[9] += err * err;
-    acc[10] += fabsf(log10f(g) - log10f(q));
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < MET_N; ++i) {
-    const float v = wave_sum(acc[i]);
-    if (lane == 0) red[i][wid] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < MET_N) {
-    const int i = threadIdx.x;
-    part[((int64_t)b * nchunk + ch) * MET_N + i] =
-        ((double)red[i][0] + (double)red[i][1]) + ((double)red[i][2] + (double)red[i][3]);
-  }
-}
-
-__global__ void metrics_final(const double* __restrict__ part, double* __restrict__ out, int B, int nchunk) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  double s[MET_N];
-  for (int i = 0; i < MET_N; ++i) s[i] = 0.0;
-  for (int c = 0; c < nchunk; ++c)
-    for (int i = 0; i < MET_N; ++i) s[i] += part[((int64_t)b * nchunk + c) * MET_N + i];
-  const double n = s[0];
-  double* o = out + (int64_t)b * 10;
-  const double inv = n > 0 ? 1.0 / n : 0.0;
-  o[0] = s[1] * inv;
-  o[1] = s[2] * inv;
-  o[2] = s[3] * inv;
-  o[3] = s[4] * inv;
-  o[4] = s[5] * inv;
-  o[5] = sqrt(s[6] * inv);
-  o[6] = sqrt(s[7] * inv);
-  const double me = s[8] * inv;
-  o[7] = sqrt(fmax(s[9] * inv - me * me, 0.0)) * 100.0;
-  o[8] = s[10] * inv;
-  o[9] = n;
-}
-
-static int metrics_chunks(int64_t HW) {
-  int64_t c = cdiv(HW, 4096);
-  return (int)(c < 1 ? 1 : (c > 256 ? 256 : c));
-}
-
 }  // namespace mdemi
 
 using namespace mdemi;
@@ -803,9 +724,10 @@ extern "C" int mdemi_depth_metrics(const float* pred, const float* gt, int32_t B
   if (!workspace) { set_error("depth_metrics: workspace required"); return MDEMI_EWORKSPACE; }
   const int nchunk = metrics_chunks((int64_t)H * W);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(metrics_partial, dim3(nchunk, B), dim3(256), 0, st, pred, gt, (double*)workspace, H, W, y0, y1,
+  // the kernels are metrics_kernel.h's, shared with the aligned form in align.hip
+  hipLaunchKernelGGL(metrics_partial<0>, dim3(nchunk, B), dim3(256), 0, st, pred, gt, (double*)workspace, H, W, y0, y1,
                      x0, x1, min_depth, max_depth, clamp_pred, nchunk);
-  hipLaunchKernelGGL(metrics_final, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, st, (const double*)workspace, out, B,
+  hipLaunchKernelGGL(metrics_final<0>, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, st, (const double*)workspace, out, B,
                      nchunk);
   return check_launch("depth_metrics");
 }

@@ -1,0 +1,136 @@
+// Depth metrics: grid (chunks, B); 11 sums per image.  One pair of kernels for mdemi_depth_metrics
+// (heads.hip, ALIGN = 0) and mdemi_depth_metrics_aligned (align.hip, ALIGN = 1): the aligned
+// form turns pred into q from the image's (s, t) on the fly and then runs the same per-pixel
+// arithmetic, chunking and combine order, so on a given q both give the same bits.
+#pragma once
+#include "common.h"
+#include "mdemi_ext.h"
+
+namespace mdemi {
+
+constexpr int MET_N = 11;  // count, a1, a2, a3, abs_rel, sq_rel, sq, sq_log, err, err^2, log10
+
+// What the ALIGN = 1 kernels read besides the metrics arguments.  It travels as a trailing
+// argument pack that is empty at ALIGN = 0, so that instantiation keeps the argument list, and
+// compiles to the instructions, it had before the switch existed.
+struct MetAlign {
+  const double* coef;  // [B][4]: s, t, n, status
+  float* aligned;      // nullable [B][H][W]: q before the clamp, on every pixel
+  int mode;            // MDEMI_ALIGN_*
+};
+__device__ __forceinline__ const MetAlign& met_align(const MetAlign& al) { return al; }
+
+// q of DESIGN §1c: formed in fp64, rounded once to fp32; a failed image keeps its prediction
+__device__ __forceinline__ float aligned_value(float p, double s, double t, bool failed, int mode, double inv_dmax) {
+  if (failed) return p;
+  if (mode == MDEMI_ALIGN_LSTSQ_DISP) return (float)(1.0 / fmax(s / (double)p + t, inv_dmax));
+  return (float)(s * (double)p + t);
+}
+
+template <int ALIGN, typename... AL>
+__global__ __launch_bounds__(256) void metrics_partial(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                       double* __restrict__ part, int H, int W, int y0, int y1, int x0,
+                                                       int x1, float dmin, float dmax, int clamp_pred, int nchunk,
+                                                       AL... al_pack) {
+  static_assert(sizeof...(AL) == (ALIGN ? 1 : 0), "ALIGN = 1 takes one MetAlign, ALIGN = 0 nothing");
+  __shared__ float red[MET_N][4];
+  const int b = blockIdx.y, ch = blockIdx.x;
+  const int64_t HW = (int64_t)H * W;
+  const int64_t per = (HW + nchunk - 1) / nchunk;
+  const int64_t p0 = (int64_t)ch * per, p1 = min(HW, p0 + per);
+  double s = 1.0, t = 0.0, inv_dmax = 0.0;
+  bool failed = true;
+  if constexpr (ALIGN != 0) {
+    const MetAlign& al = met_align(al_pack...);
+    s = al.coef[b * 4 + 0];
+    t = al.coef[b * 4 + 1];
+    failed = al.coef[b * 4 + 3] != 0.0;
+    inv_dmax = 1.0 / (double)dmax;
+  }
+  float acc[MET_N];
+#pragma unroll
+  for (int i = 0; i < MET_N; ++i) acc[i] = 0.f;
+  for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
+    const int y = (int)(p / W), x = (int)(p % W);
+    const float g = gt[(int64_t)b * HW + p];
+    float q;
+    if constexpr (ALIGN != 0) {
+      const MetAlign& al = met_align(al_pack...);
+      const bool skip = y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax);
+      if (skip && !al.aligned) continue;
+      q = aligned_value(pred[(int64_t)b * HW + p], s, t, failed, al.mode, inv_dmax);
+      if (al.aligned) al.aligned[(int64_t)b * HW + p] = q;  // off the valid set too
+      if (skip) continue;
+    } else {
+      if (y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax)) continue;
+      q = pred[(int64_t)b * HW + p];
+    }
+    if (clamp_pred) q = fminf(fmaxf(q, dmin), dmax);
+    const float th = fmaxf(g / q, q / g);
+    const float diff = g - q;
+    const float lg = logf(g), lq = logf(q);
+    const float err = lq - lg;
+    acc[0] += 1.f;
+    acc[1] += th < 1.25f ? 1.f : 0.f;
+    acc[2] += th < 1.25f * 1.25f ? 1.f : 0.f;
+    acc[3] += th < 1.25f * 1.25f * 1.25f ? 1.f : 0.f;
+    acc[4] += fabsf(diff) / g;
+    acc[5] += diff * diff / g;
+    acc[6] += diff * diff;
+    acc[7] += (lg - lq) * (lg - lq);
+    acc[8] += err;
+    acc[9] += err * err;
+    acc[10] += fabsf(log10f(g) - log10f(q));
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < MET_N; ++i) {
+    const float v = wave_sum(acc[i]);
+    if (lane == 0) red[i][wid] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < MET_N) {
+    const int i = threadIdx.x;
+    part[((int64_t)b * nchunk + ch) * MET_N + i] =
+        ((double)red[i][0] + (double)red[i][1]) + ((double)red[i][2] + (double)red[i][3]);
+  }
+}
+
+// out rows are 10 wide, or 12 with the image's (s, t) appended when ALIGN
+template <int ALIGN, typename... AL>
+__global__ void metrics_final(const double* __restrict__ part, double* __restrict__ out, int B, int nchunk,
+                              AL... al_pack) {
+  static_assert(sizeof...(AL) == (ALIGN ? 1 : 0), "ALIGN = 1 takes one MetAlign, ALIGN = 0 nothing");
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double s[MET_N];
+  for (int i = 0; i < MET_N; ++i) s[i] = 0.0;
+  for (int c = 0; c < nchunk; ++c)
+    for (int i = 0; i < MET_N; ++i) s[i] += part[((int64_t)b * nchunk + c) * MET_N + i];
+  const double n = s[0];
+  double* o = out + (int64_t)b * (ALIGN ? 12 : 10);
+  const double inv = n > 0 ? 1.0 / n : 0.0;
+  o[0] = s[1] * inv;
+  o[1] = s[2] * inv;
+  o[2] = s[3] * inv;
+  o[3] = s[4] * inv;
+  o[4] = s[5] * inv;
+  o[5] = sqrt(s[6] * inv);
+  o[6] = sqrt(s[7] * inv);
+  const double me = s[8] * inv;
+  o[7] = sqrt(fmax(s[9] * inv - me * me, 0.0)) * 100.0;
+  o[8] = s[10] * inv;
+  o[9] = n;
+  if constexpr (ALIGN != 0) {
+    const MetAlign& al = met_align(al_pack...);
+    o[10] = al.coef[b * 4 + 0];
+    o[11] = al.coef[b * 4 + 1];
+  }
+}
+
+inline int metrics_chunks(int64_t HW) {
+  int64_t c = cdiv(HW, 4096);
+  return (int)(c < 1 ? 1 : (c > 256 ? 256 : c));
+}
+
+}  // namespace mdemi

@@ -38,6 +38,7 @@ ACT_SILU, ACT_RELU_GRAD, ACT_SILU_GRAD = 6, 7, 8
 ACT_GRAD_OF = {ACT_GELU: ACT_GELU_GRAD, ACT_RELU: ACT_RELU_GRAD, ACT_SILU: ACT_SILU_GRAD}
 BINS_RELU, BINS_ELU = 0, 1  # include/mdemi_ext.h
 WL_OHWI, WL_OIHW, WL_DGRAD = 0, 1, 2  # include/mdemi_ext.h (mdemi_conv_weight_layout)
+ALIGN_MEDIAN, ALIGN_LSTSQ, ALIGN_LSTSQ_DISP = 1, 2, 3  # include/mdemi_ext.h (mdemi_depth_align)
 PAD_ZERO, PAD_REPLICATE = 0, 1
 EW_ADD, EW_SIGMOID_SCALE, EW_SIGMOID_SCALE_BWD, EW_AXPBY, EW_ACT_BWD = 0, 1, 2, 3, 4
 
@@ -240,6 +241,10 @@ _SIGS = {
     "mdemi_pad_fold_replicate": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "mdemi_depth_metrics_workspace_size": (sz, [i32, i32, i32]),
     "mdemi_depth_metrics": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "mdemi_depth_align_workspace_size": (sz, [i32, i32, i32, i32]),
+    "mdemi_depth_align": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "mdemi_depth_metrics_aligned": (ctypes.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp,
+                                                   vp, vp, vp, vp]),
     "mdemi_flip_w": (ctypes.c_int, [vp, vp, i64, i32, vp]),
     "mdemi_flip_avg_w": (ctypes.c_int, [vp, vp, vp, i64, i32, vp]),
     "mdemi_depth_export": (ctypes.c_int, [vp, i32, i32, i32, i32, i32, f32, f32, vp, f32, vp, vp, vp, vp]),

@@ -15,10 +15,13 @@ of the driver itself is unpinned; each helper is pinned by its own tests):
           predicts at half resolution (AdaBins / Depthformer v8)
   per image: metrics over crop & min_depth_eval < gt < max_depth_eval,
              pred clamped into [min_depth_eval, max_depth_eval]
+  eval.align "median" / "lstsq" / "lstsq_disp" (this framework's own key,
+  DESIGN.md 1c): pred is first aligned per image to its ground truth
 
 Every step is a libmdemi launch (flip: mdemi_flip_w / mdemi_flip_avg_w;
-resize: mdemi_bilinear_*; metrics: mdemi_depth_metrics); only the per-image
-metric rows (B x 10 fp64) come back to the host.
+resize: mdemi_bilinear_*; metrics: mdemi_depth_metrics, or mdemi_depth_align +
+mdemi_depth_metrics_aligned); only the per-image metric rows (B x 10 fp64,
+B x 12 with the alignment's s and t) come back to the host.
 """
 
 import torch

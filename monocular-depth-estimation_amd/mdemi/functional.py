@@ -2086,21 +2086,71 @@ def nchw_to_nhwc_pad(x, cp):
     return y
 
 
-def depth_metrics(pred, gt, rect, min_depth, max_depth, clamp_pred=True):
-    """Per-image [a1, a2, a3, abs_rel, sq_rel, rmse, rmse_log, silog, log_10, n_valid] (fp64) over
-    crop rect (y0, y1, x0, x1) & min_depth < gt < max_depth (utils/depth_utils.py:4-54)."""
+ALIGN_CODES = {"median": L.ALIGN_MEDIAN, "lstsq": L.ALIGN_LSTSQ, "lstsq_disp": L.ALIGN_LSTSQ_DISP}
+
+
+def _align_code(mode):
+    if mode not in ALIGN_CODES:
+        raise ValueError(f"align mode must be one of {tuple(ALIGN_CODES)}, got {mode!r}")
+    return ALIGN_CODES[mode]
+
+
+def depth_align(pred, gt, rect, min_depth, max_depth, mode):
+    """Per-image alignment of pred to gt over crop rect & min_depth < gt < max_depth (DESIGN.md
+    §1c): (B, 4) fp64 rows [s, t, n_valid, status].  mode "median": s = median(gt) / median(pred),
+    t = 0; "lstsq": least-squares scale and shift in depth; "lstsq_disp": in inverse depth.
+    status 1 marks an image that could not be aligned (s = 1, t = 0)."""
+    code = _align_code(mode)
     _require_cuda(pred, gt)
     pred, gt = _c(pred), _c(gt)
     b = pred.shape[0]
     h, w = pred.shape[-2:]
-    out = torch.empty(b, 10, device=pred.device, dtype=torch.float64)
+    coef = torch.empty(b, 4, device=pred.device, dtype=torch.float64)
     lib = L.load()
+    ws = _ws(lib.mdemi_depth_align_workspace_size(b, h, w, code), pred.device, slot=3)
+    y0, y1, x0, x1 = rect
+    L.check(lib.mdemi_depth_align(pred.data_ptr(), gt.data_ptr(), b, h, w, y0, y1, x0, x1, float(min_depth),
+                                  float(max_depth), code, coef.data_ptr(), ws.data_ptr(), L.stream()), "depth_align")
+    return coef
+
+
+def depth_metrics(pred, gt, rect, min_depth, max_depth, clamp_pred=True, align=None, return_aligned=False):
+    """Per-image [a1, a2, a3, abs_rel, sq_rel, rmse, rmse_log, silog, log_10, n_valid] (fp64) over
+    crop rect (y0, y1, x0, x1) & min_depth < gt < max_depth (utils/depth_utils.py:4-54).
+
+    align ("median", "lstsq", "lstsq_disp"): the metrics of the prediction aligned per image
+    (depth_align), rows of 12: the ten columns, then s and t.  return_aligned=True also returns
+    the aligned prediction, shaped as pred, before the clamp."""
+    if align is None:
+        if return_aligned:
+            raise ValueError("return_aligned needs an align mode")
+        _require_cuda(pred, gt)
+        pred, gt = _c(pred), _c(gt)
+        b = pred.shape[0]
+        h, w = pred.shape[-2:]
+        out = torch.empty(b, 10, device=pred.device, dtype=torch.float64)
+        lib = L.load()
+        ws = _ws(lib.mdemi_depth_metrics_workspace_size(b, h, w), pred.device, slot=3)
+        y0, y1, x0, x1 = rect
+        L.check(lib.mdemi_depth_metrics(pred.data_ptr(), gt.data_ptr(), b, h, w, y0, y1, x0, x1, float(min_depth),
+                                        float(max_depth), int(clamp_pred), out.data_ptr(), ws.data_ptr(), L.stream()),
+                "depth_metrics")
+        return out
+    code = _align_code(align)
+    pred, gt = _c(pred), _c(gt)
+    coef = depth_align(pred, gt, rect, min_depth, max_depth, align)
+    b = pred.shape[0]
+    h, w = pred.shape[-2:]
+    out = torch.empty(b, 12, device=pred.device, dtype=torch.float64)
+    aligned = torch.empty_like(pred) if return_aligned else None
+    lib = L.load()
+    # the same slot as depth_align's: stream order puts this call after the last read of it
     ws = _ws(lib.mdemi_depth_metrics_workspace_size(b, h, w), pred.device, slot=3)
     y0, y1, x0, x1 = rect
-    L.check(lib.mdemi_depth_metrics(pred.data_ptr(), gt.data_ptr(), b, h, w, y0, y1, x0, x1, float(min_depth),
-                                    float(max_depth), int(clamp_pred), out.data_ptr(), ws.data_ptr(), L.stream()),
-            "depth_metrics")
-    return out
+    L.check(lib.mdemi_depth_metrics_aligned(pred.data_ptr(), gt.data_ptr(), b, h, w, y0, y1, x0, x1, float(min_depth),
+                                            float(max_depth), int(clamp_pred), code, coef.data_ptr(), L.ptr(aligned),
+                                            out.data_ptr(), ws.data_ptr(), L.stream()), "depth_metrics_aligned")
+    return (out, aligned) if return_aligned else out
 
 
 def conv_weight_layout(w, mode, conv_shape=None):

@@ -43,6 +43,10 @@ def _args(argv):
     ap.add_argument("--grad-weight", type=float, default=None,
                     help="override the config's loss.grad_weight: add this weight times the multi-scale "
                          "gradient-matching loss to the training loss (0 switches the term off)")
+    ap.add_argument("--align", default=None, choices=["none", "median", "lstsq", "lstsq_disp"],
+                    help="override the config's eval.align: align each prediction to its ground truth before the "
+                         "metrics (validation and --test) by median scaling, or by least-squares scale and shift "
+                         "in depth (lstsq) or in inverse depth (lstsq_disp)")
     ap.add_argument("--ema", action="store_true",
                     help="with --test: evaluate the checkpoint's averaged weights (ema_state_dict)")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many optimizer steps (in all)")
@@ -57,6 +61,8 @@ def _override(opt, args):
         opt.setdefault("train", {})["ema_decay"] = args.ema_decay
     if args.grad_weight is not None:
         opt.setdefault("loss", {})["grad_weight"] = args.grad_weight
+    if args.align is not None:
+        opt.setdefault("eval", {})["align"] = args.align
     return opt
 
 
@@ -106,11 +112,12 @@ def main(argv=None) -> int:
 
     # 1. the config
     opt = _override(parse(args.opt, write_option=rank == 0 and not args.test), args)
-    from .train.builder import grad_match_config, nonfinite_policy
+    from .train.builder import eval_align, grad_match_config, nonfinite_policy
     from .train.ema import ema_config
     nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
     ema_config(opt)  # and so does a bad train.ema_decay / ema_warmup / ema_validate
     grad_match_config(opt)  # and a bad loss.grad_weight / grad_scales
+    align = eval_align(opt)  # and a bad eval.align
     if args.ema and not args.test:
         raise SystemExit("mdemi.run --ema selects the weights --test evaluates; to train with averaged weights set "
                          "train.ema_decay (or --ema-decay)")
@@ -182,6 +189,8 @@ def main(argv=None) -> int:
             rec = {"type": "test", "checkpoint": ck_path, **metrics}
             if args.ema:
                 rec["weights"] = "ema"
+            if align != "none":
+                rec["align"] = align
             if rank == 0:
                 os.makedirs(out_dir, exist_ok=True)
                 with open(os.path.join(out_dir, "log.jsonl"), "a", encoding="utf-8") as f:

@@ -191,6 +191,13 @@ def nonfinite_policy(opt):
     return policy, limit
 
 
+def eval_align(opt):
+    """eval.align, validated: "none" (also when the key is absent), "median", "lstsq" or
+    "lstsq_disp" -- the per-image alignment the evaluator applies before the metrics."""
+    from ..utils.depth_utils import check_align_mode
+    return check_align_mode(opt.get("eval", {}).get("align", "none"))
+
+
 def build_optimizer(model, opt, capturable=False):
     o = opt.get("optimizer", {})
     betas = tuple(float(b) for b in o.get("betas", (0.9, 0.999)))

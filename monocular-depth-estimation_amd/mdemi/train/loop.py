@@ -33,7 +33,7 @@ import torch
 
 from .. import _lib as L
 from ..utils.dist_utils import all_reduce_dict
-from .builder import nonfinite_policy, optimizer_steps_per_epoch
+from .builder import eval_align, nonfinite_policy, optimizer_steps_per_epoch
 from .ema import ema_config
 from .telemetry import NonFiniteStep
 
@@ -151,7 +151,9 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     (trainer.ema, train.ema_decay) it is called as validate(model) instead: on trainer.ema.module
     after ModelEma.sync_buffers -- the "valid" record then carries "weights": "ema" and best.pth
     is chosen on its abs_rel -- and, under train.ema_validate "both", on trainer.model too, for
-    a second record with "weights": "model".  telemetry defaults to
+    a second record with "weights": "model".  With eval.align other than "none" the caller's
+    validate() reports aligned metrics; the record then carries "align": MODE and best.pth is
+    chosen on the aligned abs_rel.  telemetry defaults to
     trainer.telemetry.  ``best`` is (abs_rel, epoch, iter) of the best checkpoint so far
     (a resumed run).  Rank 0 writes out_dir/log.jsonl -- {"type": "train", ...} every
     train.print_freq steps, {"type": "valid", ...} per validation -- and latest.pth /
@@ -179,6 +181,7 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     ema_validate = ema_config(opt)[2]
 
     policy, max_skips = nonfinite_policy(opt)
+    align = eval_align(opt)
     skip_mode = policy == "skip"
     guard = getattr(trainer.optimizer, "skipped_steps", None) if skip_mode else None
     if skip_mode and (guard is None or not getattr(trainer.optimizer, "skip_nonfinite", True)):
@@ -308,6 +311,10 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
             best_value, best_epoch, best_iter = metrics["abs_rel"], epoch, it
         rec = {"type": "valid", "epoch": epoch, "iter": it, "step": done, **metrics, "best": improved}
         recs = [rec]
+        if align != "none":  # the metrics, and so the choice of best.pth, are those of aligned predictions
+            rec["align"] = align
+            if raw is not None:
+                raw["align"] = align
         if ema is not None:
             rec["weights"] = "ema"
             if raw is not None:  # for the record only: best.pth is chosen on the averaged weights

@@ -21,7 +21,7 @@ StepRecord = namedtuple("StepRecord", "loss grad_sumsq index flags")
 Drained = namedtuple("Drained", "records dropped pushed")
 
 _STATE_BYTES = ctypes.sizeof(L.TelemetryState)
-_REC_DTYPE = np.dtype([("loss", "<f4"), ("grad_sumsq", "<f4"), ("index", "<i4"), ("flags", "<u4")])
+_REC_DTYPE = np.dtype(L.StepRecord)  # the fields of mdemi_step_record, as the header declares them
 assert _REC_DTYPE.itemsize == ctypes.sizeof(L.StepRecord) == 16 and _STATE_BYTES == 16
 
 

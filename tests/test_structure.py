@@ -20,8 +20,8 @@ def test_library_exports_every_header_symbol():
     assert len(declared) > 30
     for name in sorted(declared):
         assert hasattr(lib, name), f"libmdemi.so does not export {name}"
-    # and the ctypes table covers the header
-    assert declared <= set(_lib.exported_symbols()), declared - set(_lib.exported_symbols())
+    # and the ctypes binding is exactly the header's set
+    assert declared == set(_lib.exported_symbols()), declared ^ set(_lib.exported_symbols())
 
 
 def test_library_version_and_error_path():

@@ -480,6 +480,49 @@ int mdemi_gradmatch_fwd(const float* pred, const float* gt, float* loss, float* 
 int mdemi_gradmatch_bwd(const float* pred, const float* gt, const float* wk, const float* dloss, float* dpred,
                         int32_t B, int32_t H, int32_t W, float min_depth, int32_t scales, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Scale- and shift-invariant loss (cfg loss.ssi_weight / ssi_space /        */
+/* ssi_trim / ssi_norm; this framework's own definition, DESIGN.md 1c -- no  */
+/* reference parity).  pred, gt [B][H][W].  Per image, on V = gt > min_depth */
+/* (n pixels): x, y = p, g (DEPTH) or 1/p, 1/g (DISP, fp64 reciprocals);     */
+/* Sx, Sy, Sxx, Sxy, Syy in fp64; det = n Sxx - Sx^2, s = (n Sxy - Sx Sy) /  */
+/* det, t = (Sxx Sy - Sx Sxy) / det (mdemi_depth_align's LSTSQ solve);       */
+/* r = s x + t - y in fp64, rho = |(float) r|.  Trimming, trim in [0, 0.5]:  */
+/* u = n - floor((double) trim * n), tau = the u-th smallest rho (exact, on  */
+/* the fp32 values), K = {rho <= tau} with every tie kept, U = |K|,          */
+/* Q = sum_K r^2, A = sum_K r x, Bt = sum_K r; trim == 0: K = V, U = n and   */
+/* A = Bt = 0 by definition.  norm GT_VAR: v = Syy / n - (Sy / n)^2, else    */
+/* v = 1.  An image is skipped -- loss 0, gradient exactly 0, out of the     */
+/* per-image mean -- when n == 0, det is finite and <= 0, or v is finite and */
+/* <= 0; a non-finite det (a NaN / inf prediction, p = 0 under DISP) is not: */
+/* the loss is NaN.  per_image 0: loss = sum_b (Q_b / v_b) / (2 sum_b U_b),  */
+/* w_b = 1 / (v_b sum U); 1: the mean over the images used of                */
+/* Q_b / (2 U_b v_b), w_b = 1 / (U_b v_b images used); none used gives 0.    */
+/* fwd writes loss[0] and coef [B][8] (fp64) = s, t, tau, a = w s, e0, e1,   */
+/* e2, status (1: skipped); bwd recomputes r and rho with the forward's      */
+/* arithmetic, so K is the forward's bit for bit, and writes                 */
+/*   dpred = dloss[0] * (k r a + e0 + e1 x + e2 y) * dx/dp,  dx/dp = 1 or    */
+/*   -1 / p^2; e0 + e1 x + e2 y = w [(A - Bt Sx / n)(n y - Sy - 2 s (n x -   */
+/*   Sx)) / det - Bt s / n], the dependence of (s, t) on pred, exactly 0     */
+/*   without trimming; exactly 0 where gt <= min_depth.                      */
+/* Neither synchronises or allocates; the select's counters are cleared on   */
+/* the stream; fp64 partials combine in a fixed order and only integer       */
+/* atomics are used: two runs give the same bits.  Any H, W and base; H * W  */
+/* % 4 == 0 with 16-byte aligned bases takes the 4-pixel vector path.        */
+/* workspace: mdemi_ssi_workspace_size bytes (trimmed = trim > 0 adds a      */
+/* [B][H][W] plane of rho), 16-byte aligned.  B is 1..65535.                 */
+/* ------------------------------------------------------------------------ */
+#define MDEMI_SSI_DEPTH 0
+#define MDEMI_SSI_DISP 1
+#define MDEMI_SSI_NORM_NONE 0
+#define MDEMI_SSI_NORM_GT_VAR 1
+size_t mdemi_ssi_workspace_size(int32_t B, int32_t H, int32_t W, int32_t trimmed);
+int mdemi_ssi_fwd(const float* pred, const float* gt, float* loss, double* coef, int32_t B, int32_t H, int32_t W,
+                  float min_depth, int32_t space, float trim, int32_t norm, int32_t per_image, void* workspace,
+                  void* stream);
+int mdemi_ssi_bwd(const float* pred, const float* gt, const double* coef, const float* dloss, float* dpred, int32_t B,
+                  int32_t H, int32_t W, float min_depth, int32_t space, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

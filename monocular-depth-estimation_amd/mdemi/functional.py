@@ -1311,6 +1311,72 @@ def grad_match_loss(pred, gt, min_depth=1e-3, scales=4, per_image=False):
 
 
 # --------------------------------------------------------------------------
+# Scale- and shift-invariant loss
+# --------------------------------------------------------------------------
+
+SSI_SPACES = ("depth", "disp")  # MDEMI_SSI_DEPTH / _DISP
+SSI_NORMS = ("none", "gt_var")  # MDEMI_SSI_NORM_NONE / _GT_VAR
+
+
+def check_ssi_options(space, trim, norm, what=("space", "trim", "norm")):
+    """(space, float(trim), norm), validated; ``what`` names the three in the error text."""
+    if space not in SSI_SPACES:
+        raise ValueError(f"{what[0]} must be one of {SSI_SPACES}, got {space!r}")
+    if isinstance(trim, bool) or not isinstance(trim, (int, float)) or not math.isfinite(trim) or not 0 <= trim <= 0.5:
+        raise ValueError(f"{what[1]} must be a finite number in [0, 0.5], got {trim!r}")
+    if norm not in SSI_NORMS:
+        raise ValueError(f"{what[2]} must be one of {SSI_NORMS}, got {norm!r}")
+    return space, float(trim), norm
+
+
+class _SSIFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, min_depth, space, trim, norm, per_image):
+        _require_cuda(pred, gt)
+        pred = _c(pred)
+        gt = _c(gt)
+        H, W = pred.shape[-2:]
+        B = pred.numel() // (H * W)
+        loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+        coef = torch.empty(B, 8, device=pred.device, dtype=torch.float64)
+        lib = L.load()
+        ws = L.workspace(lib.mdemi_ssi_workspace_size(B, H, W, int(trim > 0)), pred.device, slot=5)
+        L.check(lib.mdemi_ssi_fwd(pred.data_ptr(), gt.data_ptr(), loss.data_ptr(), coef.data_ptr(), B, H, W,
+                                  float(min_depth), space, trim, norm, int(per_image), ws.data_ptr(), L.stream()),
+                "ssi_fwd")
+        ctx.save_for_backward(pred, gt, coef)
+        ctx.cfg = (min_depth, space)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, gt, coef = ctx.saved_tensors
+        min_depth, space = ctx.cfg
+        H, W = pred.shape[-2:]
+        B = pred.numel() // (H * W)
+        dpred = torch.empty_like(pred)
+        dl = _c(dloss.reshape(1).to(torch.float32))
+        L.call("mdemi_ssi_bwd", pred.data_ptr(), gt.data_ptr(), coef.data_ptr(), dl.data_ptr(), dpred.data_ptr(),
+               B, H, W, float(min_depth), space, L.stream())
+        return dpred, None, None, None, None, None, None
+
+
+def ssi_loss(pred, gt, min_depth=1e-3, space="depth", trim=0.0, norm="none", per_image=False):
+    """Scale- and shift-invariant loss (MiDaS / DPT) of pred against gt, both (B,1,H,W) or (B,H,W):
+    per image, half the mean squared residual of the least-squares fit s x + t to y over
+    gt > min_depth, with x, y the depths (``space`` "depth") or their reciprocals ("disp").
+    ``trim`` in [0, 0.5] drops that share of the largest absolute residuals; ``norm`` "gt_var"
+    divides by the variance of y.  Reduced over the batch or per image and then averaged over the
+    images that have a fit."""
+    space, trim, norm = check_ssi_options(space, trim, norm)
+    if pred.dim() < 3 or pred.shape != gt.shape or pred.numel() == 0 or \
+            pred.numel() != pred.shape[0] * pred.shape[-2] * pred.shape[-1]:
+        raise ValueError(f"ssi_loss: pred and gt must both be (B,1,H,W) or (B,H,W) and non-empty, got "
+                         f"{tuple(pred.shape)} and {tuple(gt.shape)}")
+    return _SSIFn.apply(pred, gt, min_depth, SSI_SPACES.index(space), trim, SSI_NORMS.index(norm), bool(per_image))
+
+
+# --------------------------------------------------------------------------
 # Resampling / layout
 # --------------------------------------------------------------------------
 

@@ -43,6 +43,9 @@ def _args(argv):
     ap.add_argument("--grad-weight", type=float, default=None,
                     help="override the config's loss.grad_weight: add this weight times the multi-scale "
                          "gradient-matching loss to the training loss (0 switches the term off)")
+    ap.add_argument("--ssi-weight", type=float, default=None,
+                    help="override the config's loss.ssi_weight: add this weight times the scale- and "
+                         "shift-invariant loss to the training loss (0 switches the term off)")
     ap.add_argument("--align", default=None, choices=["none", "median", "lstsq", "lstsq_disp"],
                     help="override the config's eval.align: align each prediction to its ground truth before the "
                          "metrics (validation and --test) by median scaling, or by least-squares scale and shift "
@@ -61,6 +64,8 @@ def _override(opt, args):
         opt.setdefault("train", {})["ema_decay"] = args.ema_decay
     if args.grad_weight is not None:
         opt.setdefault("loss", {})["grad_weight"] = args.grad_weight
+    if args.ssi_weight is not None:
+        opt.setdefault("loss", {})["ssi_weight"] = args.ssi_weight
     if args.align is not None:
         opt.setdefault("eval", {})["align"] = args.align
     return opt
@@ -112,11 +117,12 @@ def main(argv=None) -> int:
 
     # 1. the config
     opt = _override(parse(args.opt, write_option=rank == 0 and not args.test), args)
-    from .train.builder import eval_align, grad_match_config, nonfinite_policy
+    from .train.builder import eval_align, grad_match_config, nonfinite_policy, ssi_config
     from .train.ema import ema_config
     nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
     ema_config(opt)  # and so does a bad train.ema_decay / ema_warmup / ema_validate
     grad_match_config(opt)  # and a bad loss.grad_weight / grad_scales
+    ssi_config(opt)  # and a bad loss.ssi_weight / ssi_space / ssi_trim / ssi_norm
     align = eval_align(opt)  # and a bad eval.align
     if args.ema and not args.test:
         raise SystemExit("mdemi.run --ema selects the weights --test evaluates; to train with averaged weights set "

@@ -23,6 +23,13 @@ unchanged, onto this framework's objects:
                            or per batch as loss.per_image says; ODA2: averaged over every output
                            like si_weight x SILog.  loss.grad_scales: its scales, 1..4 (default 4).
                            This framework's own keys and definition (a decision)
+  loss.ssi_weight       -> absent / 0: off.  A finite float > 0: + ssi_weight x SSILoss, the scale- and
+                           shift-invariant data term on the same (resized) depth, reduced as
+                           loss.per_image says; ODA2: averaged over every output.  loss.ssi_space
+                           "depth" (default) | "disp", loss.ssi_trim in [0, 0.5] (default 0),
+                           loss.ssi_norm "none" (default) | "gt_var".  While it is on, loss.si_weight
+                           also weighs SILog on the single-output models, and si_weight 0 launches
+                           no SILog.  This framework's own keys and definition
   optimizer.lr/weight_decay/betas/eps/same_lr -> FusedAdamW; with get_1x_lr_params
                         (unet_adaptive_bins.py:111-117) and same_lr false: two groups,
                         encoder at lr/10, the rest at lr
@@ -55,7 +62,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .loss import BinsChamferLoss, GradMatchLoss, SILogLoss, resize_to_gt
+from .loss import BinsChamferLoss, GradMatchLoss, SILogLoss, SSILoss, resize_to_gt
 from .optim import FusedAdamW, OneCycleLR
 
 MODEL_NAMES = ("adabins", "newcrfs", "depthformer_v8", "oda2_red_order_swin2")
@@ -102,9 +109,10 @@ def build_model(opt, drop_path=None):
 # loss.* keys of the in-scope reference configs; sog_weight names a loss term this framework
 # does not implement (0.0 in every in-scope config) and reduction_ratio configures only that
 # term -- a nonzero sog_weight is refused rather than silently dropped
-# grad_weight / grad_scales are this framework's own keys (the gradient-matching term)
+# grad_weight / grad_scales (the gradient-matching term) and ssi_weight / ssi_space / ssi_trim / ssi_norm
+# (the scale- and shift-invariant term) are this framework's own keys
 LOSS_KEYS = ("alpha", "beta", "per_image", "chamfer_weight", "si_weight", "sog_weight", "reduction_ratio",
-             "grad_weight", "grad_scales")
+             "grad_weight", "grad_scales", "ssi_weight", "ssi_space", "ssi_trim", "ssi_norm")
 
 
 def grad_match_config(opt):
@@ -118,10 +126,26 @@ def grad_match_config(opt):
     return float(w), check_grad_scales(lo.get("grad_scales", 4), "loss.grad_scales")
 
 
+def ssi_config(opt):
+    """(loss.ssi_weight, loss.ssi_space, loss.ssi_trim, loss.ssi_norm), validated: a finite weight
+    >= 0 (absent: 0.0, the term is off), "depth" (default) or "disp", a finite trim in [0, 0.5]
+    (default 0.0) and "none" (default) or "gt_var"."""
+    lo = opt.get("loss", {})
+    w = lo.get("ssi_weight", 0.0)
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or w < 0:
+        raise ValueError(f"loss.ssi_weight must be a finite number >= 0, got {w!r}")
+    from ..functional import check_ssi_options
+    return (float(w),) + check_ssi_options(lo.get("ssi_space", "depth"), lo.get("ssi_trim", 0.0),
+                                           lo.get("ssi_norm", "none"),
+                                           ("loss.ssi_space", "loss.ssi_trim", "loss.ssi_norm"))
+
+
 class TrainLoss:
     """SILog on the depth (+ chamfer_weight x the bin chamfer loss on AdaBins' edges /
     Depthformer's centres when loss.chamfer_weight > 0, + grad_weight x the multi-scale
-    gradient-matching loss on the same depth when loss.grad_weight > 0)."""
+    gradient-matching loss on the same depth when loss.grad_weight > 0, + ssi_weight x the
+    scale- and shift-invariant loss on the same depth when loss.ssi_weight > 0; with that term
+    on, si_weight weighs SILog on every model and si_weight 0 leaves SILog out)."""
 
     def __init__(self, opt, model_name):
         lo = opt.get("loss", {})
@@ -132,6 +156,7 @@ class TrainLoss:
             raise ValueError(f"loss.sog_weight={lo['sog_weight']}: the SOG loss term is not implemented "
                              "(every in-scope reference config sets it to 0.0)")
         self.grad_weight, grad_scales = grad_match_config(opt)
+        self.ssi_weight, ssi_space, ssi_trim, ssi_norm = ssi_config(opt)
         dmin, _ = _depth_range(opt)
         self.silog = SILogLoss(alpha=float(lo.get("alpha", 10.0)), beta=float(lo.get("beta", 0.15)),
                                per_image=bool(lo.get("per_image", False)), min_depth=dmin)
@@ -140,27 +165,43 @@ class TrainLoss:
         # weight 0 (or no key): no module, nothing of the term is launched
         self.grad = GradMatchLoss(grad_scales, per_image=self.silog.per_image, min_depth=dmin) \
             if self.grad_weight > 0 else None
+        self.ssi = SSILoss(ssi_space, ssi_trim, ssi_norm, per_image=self.silog.per_image, min_depth=dmin) \
+            if self.ssi_weight > 0 else None
         self.multi = model_name == "oda2_red_order_swin2"
         self.si_weight = float(lo.get("si_weight", 1.0))
 
     def __call__(self, out, gt):
         if self.multi:  # (out, outs, attn): every output, each upsampled to the GT
             outs = [resize_to_gt(o, gt) for o in out[1]]
-            loss = self.silog(outs[0], gt)
-            for o in outs[1:]:
-                loss = loss + self.silog(o, gt)
-            loss = loss * (self.si_weight / len(outs))
-            if self.grad is not None:
-                gm = self.grad(outs[0], gt)
+
+            def mean_of(term, weight):
+                total = term(outs[0], gt)
                 for o in outs[1:]:
-                    gm = gm + self.grad(o, gt)
-                loss = loss + gm * (self.grad_weight / len(outs))
+                    total = total + term(o, gt)
+                return total * (weight / len(outs))
+
+            loss = None if self.ssi is not None and self.si_weight == 0 else mean_of(self.silog, self.si_weight)
+            if self.grad is not None:
+                gm = mean_of(self.grad, self.grad_weight)
+                loss = gm if loss is None else loss + gm
+            if self.ssi is not None:
+                ssi = mean_of(self.ssi, self.ssi_weight)
+                loss = ssi if loss is None else loss + ssi
             return loss
         pred = out[0] if isinstance(out, tuple) else out
-        pred = resize_to_gt(pred, gt)  # a half-resolution prediction, once for both terms
-        loss = self.silog(pred, gt)
+        pred = resize_to_gt(pred, gt)  # a half-resolution prediction, once for every term
+        if self.ssi is None:  # si_weight is not read on this path while the SSI term is off
+            loss = self.silog(pred, gt)
+        elif self.si_weight == 0:
+            loss = None
+        else:
+            loss = self.silog(pred, gt) if self.si_weight == 1 else self.si_weight * self.silog(pred, gt)
         if self.grad is not None:
-            loss = loss + self.grad_weight * self.grad(pred, gt)
+            gm = self.grad_weight * self.grad(pred, gt)
+            loss = gm if loss is None else loss + gm
+        if self.ssi is not None:
+            ssi = self.ssi_weight * self.ssi(pred, gt)
+            loss = ssi if loss is None else loss + ssi
         if self.chamfer is not None:
             loss = loss + self.w * self.chamfer(out[1], gt)
         return loss

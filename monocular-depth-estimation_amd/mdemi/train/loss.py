@@ -4,7 +4,8 @@ upstream AdaBins' BinsChamferLoss -- the reference's loss module is absent).
 AdaBins / Depthformer predictions are at half resolution and are resized to
 the ground truth with bilinear align_corners=True first (upstream AdaBins
 convention; parity unpinned).  The multi-scale gradient-matching loss (config keys
-loss.grad_weight / loss.grad_scales) is this framework's own term."""
+loss.grad_weight / loss.grad_scales) and the scale- and shift-invariant loss (loss.ssi_weight /
+ssi_space / ssi_trim / ssi_norm) are this framework's own terms."""
 import torch.nn as nn
 
 from .. import functional as mf
@@ -46,6 +47,24 @@ class GradMatchLoss(nn.Module):
     def forward(self, pred, gt):
         """pred (B,1,h,w), gt (B,1,H,W); a half-resolution prediction is resized to the GT first."""
         return mf.grad_match_loss(resize_to_gt(pred, gt), gt, self.min_depth, self.scales, self.per_image)
+
+
+class SSILoss(nn.Module):
+    """Scale- and shift-invariant loss (MiDaS / DPT / Depth Anything's data term): per image, half
+    the mean squared residual of the least-squares fit s x + t to y over the valid pixels, x and
+    y the depths (``space`` "depth") or the inverse depths ("disp"); ``trim`` drops that share of
+    the largest absolute residuals, ``norm`` "gt_var" divides by the variance of y -- per batch
+    or per image, the switch SILog reads (config keys loss.ssi_*)."""
+
+    def __init__(self, space="depth", trim=0.0, norm="none", per_image=False, min_depth=1e-3):
+        super().__init__()
+        self.space, self.trim, self.norm = mf.check_ssi_options(space, trim, norm)
+        self.per_image, self.min_depth = bool(per_image), float(min_depth)
+
+    def forward(self, pred, gt):
+        """pred (B,1,h,w), gt (B,1,H,W); a half-resolution prediction is resized to the GT first."""
+        return mf.ssi_loss(resize_to_gt(pred, gt), gt, self.min_depth, self.space, self.trim, self.norm,
+                           self.per_image)
 
 
 class BinsChamferLoss(nn.Module):

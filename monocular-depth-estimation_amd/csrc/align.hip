@@ -10,31 +10,15 @@
 //     block tree, per-chunk partials summed in chunk order by one thread per image.
 // Every sweep has grid (chunks, B) with the chunking of the metrics kernel.
 #include "common.h"
+#include "image_reduce.h"
 #include "mdemi_ext.h"
 #include "metrics_kernel.h"
 
 namespace mdemi {
 
-constexpr int AL_BINS = 2048;  // 11 bits; the last pass uses 1024 of them
 constexpr int AL_SEL = 4;      // pred low, pred high, gt low, gt high
 constexpr int AL_STATE = 12;   // uint32 per image: prefix[4], rank[4], n, 3 unused
 constexpr int LSQ_N = 5;       // n, Sx, Sy, Sxx, Sxy
-
-__host__ __device__ inline int al_shift(int pass) { return pass == 0 ? 21 : (pass == 1 ? 10 : 0); }
-__host__ __device__ inline int al_bins(int pass) { return pass == 2 ? 1024 : 2048; }
-// key bits already fixed by the passes before `pass`
-__host__ __device__ inline uint32_t al_mask(int pass) {
-  return pass == 0 ? 0u : (pass == 1 ? 0xFFE00000u : 0xFFFFFC00u);
-}
-
-// monotone in the float order, total on the bits: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN
-__device__ __forceinline__ uint32_t al_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float al_unkey(uint32_t k) {
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
 
 // hist[b][sel][bin] += number of valid pixels of chunk (blockIdx.x) whose key starts with
 // selection sel's prefix and continues with bin.  hist is all zero on entry.
@@ -42,24 +26,22 @@ __global__ __launch_bounds__(256) void align_hist(const float* __restrict__ pred
                                                   const uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
                                                   int H, int W, int y0, int y1, int x0, int x1, float dmin, float dmax,
                                                   int nchunk, int pass) {
-  __shared__ uint32_t h[AL_SEL][AL_BINS];
-  const int b = blockIdx.y, ch = blockIdx.x;
+  __shared__ uint32_t h[AL_SEL][RS_BINS];
+  const int b = blockIdx.y;
   const int64_t HW = (int64_t)H * W;
-  const int64_t per = (HW + nchunk - 1) / nchunk;
-  const int64_t p0 = (int64_t)ch * per, p1 = min(HW, p0 + per);
-  const int shift = al_shift(pass), nb = al_bins(pass);
-  const uint32_t mask = al_mask(pass);
+  int64_t p0, p1;
+  met_chunk(HW, nchunk, p0, p1);
+  const int shift = rs_shift(pass), nb = rs_bins(pass);
+  const uint32_t mask = rs_mask(pass);
   uint32_t pre[AL_SEL];
 #pragma unroll
   for (int s = 0; s < AL_SEL; ++s) pre[s] = pass == 0 ? 0u : state[b * AL_STATE + s];
   const bool two_p = pre[1] != pre[0], two_g = pre[3] != pre[2];  // uniform over the block
-  for (int i = threadIdx.x; i < AL_SEL * AL_BINS; i += 256) (&h[0][0])[i] = 0u;
-  __syncthreads();
+  rs_hist_zero(&h[0][0], AL_SEL * RS_BINS);
   for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-    const int y = (int)(p / W), x = (int)(p % W);
     const float g = gt[(int64_t)b * HW + p];
-    if (y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax)) continue;
-    const uint32_t kp = al_key(pred[(int64_t)b * HW + p]), kg = al_key(g);
+    if (!met_valid(p, W, g, y0, y1, x0, x1, dmin, dmax)) continue;
+    const uint32_t kp = rs_key(pred[(int64_t)b * HW + p]), kg = rs_key(g);
     const uint32_t bp = (kp >> shift) & (uint32_t)(nb - 1), bg = (kg >> shift) & (uint32_t)(nb - 1);
     if ((kp & mask) == pre[0]) atomicAdd(&h[0][bp], 1u);
     if (two_p && (kp & mask) == pre[1]) atomicAdd(&h[1][bp], 1u);
@@ -67,76 +49,46 @@ __global__ __launch_bounds__(256) void align_hist(const float* __restrict__ pred
     if (two_g && (kg & mask) == pre[3]) atomicAdd(&h[3][bg], 1u);
   }
   __syncthreads();
-  uint32_t* out = hist + (int64_t)b * AL_SEL * AL_BINS;
+  uint32_t* out = hist + (int64_t)b * AL_SEL * RS_BINS;
 #pragma unroll
   for (int s = 0; s < AL_SEL; ++s) {
     if ((s == 1 && !two_p) || (s == 3 && !two_g)) continue;
-    for (int i = threadIdx.x; i < nb; i += 256) {
-      const uint32_t c = h[s][i];
-      if (c) atomicAdd(&out[s * AL_BINS + i], c);
-    }
+    rs_hist_flush(h[s], out + s * RS_BINS, nb);
   }
 }
 
 // One block per image, one wave per selection: find the bin that holds the selection's rank,
-// append it to the prefix, make the rank relative to that bin, and clear the image's histograms
-// for the next pass.  Pass 0 also derives n and the four ranks; pass 2 writes coef.
+// append it to the prefix, make the rank relative to that bin (rs_rank_step), and clear the
+// image's histograms for the next pass.  Pass 0 also derives n and the four ranks; pass 2 writes coef.
 __global__ __launch_bounds__(256) void align_select(uint32_t* __restrict__ state, uint32_t* __restrict__ hist,
                                                     double* __restrict__ coef, int pass) {
   __shared__ uint32_t key_s[AL_SEL];
-  const int b = blockIdx.x, sel = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x, sel = threadIdx.x >> 6;
   uint32_t* st = state + b * AL_STATE;
-  uint32_t* hb = hist + (int64_t)b * AL_SEL * AL_BINS;
+  uint32_t* hb = hist + (int64_t)b * AL_SEL * RS_BINS;
   const int arr = sel >> 1;
   const uint32_t pre_lo = pass == 0 ? 0u : st[arr * 2], pre_hi = pass == 0 ? 0u : st[arr * 2 + 1];
-  const uint32_t my_pre = (sel & 1) ? pre_hi : pre_lo;
   // align_hist filled the high selection's table only where the two prefixes differ
-  const uint32_t* table = hb + (pre_lo == pre_hi ? arr * 2 : sel) * AL_BINS;
-  const int per = al_bins(pass) / 64;  // contiguous bins per lane
-  uint32_t sum = 0;
-  for (int i = 0; i < per; ++i) sum += table[lane * per + i];
-  uint32_t incl = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t v = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += v;
-  }
-  const uint32_t total = __shfl(incl, 63, 64), excl = incl - sum;
-  uint32_t rank;
-  if (pass == 0)
-    rank = total ? ((sel & 1) ? total / 2 : (total - 1) / 2) : 0u;
-  else
-    rank = st[AL_SEL + sel];
-  bool found = false;
-  uint32_t new_pre = my_pre, new_rank = rank;
-  if (rank >= excl && rank < incl) {  // at most one lane; none when the image has no valid pixel
-    uint32_t r = rank - excl;
-    for (int i = 0; i < per; ++i) {
-      const uint32_t c = table[lane * per + i];
-      if (r < c) {
-        found = true;
-        new_pre = my_pre | ((uint32_t)(lane * per + i) << al_shift(pass));
-        new_rank = r;
-        break;
-      }
-      r -= c;
-    }
-  }
+  const uint32_t* table = hb + (pre_lo == pre_hi ? arr * 2 : sel) * RS_BINS;
+  const RsStep r = rs_rank_step(table, pass, (sel & 1) ? pre_hi : pre_lo, [&](uint32_t total) {
+    if (pass != 0) return st[AL_SEL + sel];
+    return total ? ((sel & 1) ? total / 2 : (total - 1) / 2) : 0u;
+  });
   if (threadIdx.x < AL_SEL) key_s[threadIdx.x] = 0u;
   __syncthreads();  // every read of state and of the histograms is done
-  if (found) {
-    st[sel] = new_pre;
-    st[AL_SEL + sel] = new_rank;
-    key_s[sel] = new_pre;
+  if (r.found) {
+    st[sel] = r.prefix;
+    st[AL_SEL + sel] = r.rank;
+    key_s[sel] = r.prefix;
   }
-  if (pass == 0 && threadIdx.x == 0) st[2 * AL_SEL] = total;  // n: every valid pixel is in pass 0's pred table
-  for (int i = threadIdx.x; i < AL_SEL * AL_BINS; i += 256) hb[i] = 0u;
+  if (pass == 0 && threadIdx.x == 0) st[2 * AL_SEL] = r.total;  // n: every valid pixel is in pass 0's pred table
+  for (int i = threadIdx.x; i < AL_SEL * RS_BINS; i += 256) hb[i] = 0u;
   if (pass != 2) return;
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t n = st[2 * AL_SEL];
-    const double mp = 0.5 * ((double)al_unkey(key_s[0]) + (double)al_unkey(key_s[1]));
-    const double mg = 0.5 * ((double)al_unkey(key_s[2]) + (double)al_unkey(key_s[3]));
+    const double mp = 0.5 * ((double)rs_unkey(key_s[0]) + (double)rs_unkey(key_s[1]));
+    const double mg = 0.5 * ((double)rs_unkey(key_s[2]) + (double)rs_unkey(key_s[3]));
     const bool ok = n > 0 && mp > 0.0;
     coef[b * 4 + 0] = ok ? mg / mp : 1.0;
     coef[b * 4 + 1] = 0.0;
@@ -145,50 +97,33 @@ __global__ __launch_bounds__(256) void align_select(uint32_t* __restrict__ state
   }
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // part[b][chunk][5] = n, Sx, Sy, Sxx, Sxy of the chunk's valid pixels; x, y = p, g or 1/p, 1/g
 template <bool DISP>
 __global__ __launch_bounds__(256) void align_lsq_partial(const float* __restrict__ pred, const float* __restrict__ gt,
                                                          double* __restrict__ part, int H, int W, int y0, int y1,
                                                          int x0, int x1, float dmin, float dmax, int nchunk) {
-  __shared__ double red[LSQ_N][4];
-  const int b = blockIdx.y, ch = blockIdx.x;
+  const int b = blockIdx.y;
   const int64_t HW = (int64_t)H * W;
-  const int64_t per = (HW + nchunk - 1) / nchunk;
-  const int64_t p0 = (int64_t)ch * per, p1 = min(HW, p0 + per);
+  int64_t p0, p1;
+  met_chunk(HW, nchunk, p0, p1);
   double acc[LSQ_N];
 #pragma unroll
   for (int i = 0; i < LSQ_N; ++i) acc[i] = 0.0;
   for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-    const int y = (int)(p / W), x = (int)(p % W);
     const float g = gt[(int64_t)b * HW + p];
-    if (y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax)) continue;
-    double xv = (double)pred[(int64_t)b * HW + p], yv = (double)g;
-    if (DISP) { xv = 1.0 / xv; yv = 1.0 / yv; }
+    if (!met_valid(p, W, g, y0, y1, x0, x1, dmin, dmax)) continue;
+    const double xv = lsq_operand<DISP>(pred[(int64_t)b * HW + p]), yv = lsq_operand<DISP>(g);
     acc[0] += 1.0;
     acc[1] += xv;
     acc[2] += yv;
     acc[3] += xv * xv;
     acc[4] += xv * yv;
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < LSQ_N; ++i) {
-    const double v = wave_sum_d(acc[i]);
-    if (lane == 0) red[i][wid] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < LSQ_N) {
-    const int i = threadIdx.x;
-    part[((int64_t)b * nchunk + ch) * LSQ_N + i] = (red[i][0] + red[i][1]) + (red[i][2] + red[i][3]);
-  }
+  block_store_pairwise(acc, part + ((int64_t)b * nchunk + blockIdx.x) * LSQ_N);
 }
 
+// One thread per image adds its chunks in chunk order.  (The lane-strided chunk_sums_strided is
+// faster but changes the last bits of the evaluation numbers: a change of its own, not made here.)
 __global__ void align_lsq_solve(const double* __restrict__ part, double* __restrict__ coef, int B, int nchunk) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
@@ -196,11 +131,11 @@ __global__ void align_lsq_solve(const double* __restrict__ part, double* __restr
   for (int i = 0; i < LSQ_N; ++i) s[i] = 0.0;
   for (int c = 0; c < nchunk; ++c)
     for (int i = 0; i < LSQ_N; ++i) s[i] += part[((int64_t)b * nchunk + c) * LSQ_N + i];
-  const double n = s[0], sx = s[1], sy = s[2], sxx = s[3], sxy = s[4];
-  const double det = n * sxx - sx * sx;
-  const bool ok = n > 0 && isfinite(det) && det > 0.0;
-  coef[b * 4 + 0] = ok ? (n * sxy - sx * sy) / det : 1.0;
-  coef[b * 4 + 1] = ok ? (sxx * sy - sx * sxy) / det : 0.0;
+  const double n = s[0];
+  const LsqFit f = lsq_fit(n, s[1], s[2], s[3], s[4]);
+  const bool ok = n > 0 && isfinite(f.det) && f.det > 0.0;
+  coef[b * 4 + 0] = ok ? f.s : 1.0;
+  coef[b * 4 + 1] = ok ? f.t : 0.0;
   coef[b * 4 + 2] = n;
   coef[b * 4 + 3] = ok ? 0.0 : 1.0;
 }
@@ -214,7 +149,7 @@ using namespace mdemi;
 
 extern "C" size_t mdemi_depth_align_workspace_size(int32_t B, int32_t H, int32_t W, int32_t mode) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  if (mode == MDEMI_ALIGN_MEDIAN) return align_state_bytes(B) + (size_t)B * AL_SEL * AL_BINS * sizeof(uint32_t);
+  if (mode == MDEMI_ALIGN_MEDIAN) return align_state_bytes(B) + (size_t)B * AL_SEL * RS_BINS * sizeof(uint32_t);
   return align_up((size_t)B * metrics_chunks((int64_t)H * W) * LSQ_N * sizeof(double), 256);
 }
 

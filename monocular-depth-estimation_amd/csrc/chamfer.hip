@@ -68,10 +68,8 @@ __global__ void __launch_bounds__(CH_NT) chamfer_partial(const float* __restrict
     ny += 1.0;
   }
   // fixed-order block sums of (dy, ny)
-  for (int o = 32; o > 0; o >>= 1) {
-    dy += __shfl_xor(dy, o, 64);
-    ny += __shfl_xor(ny, o, 64);
-  }
+  dy = wave_sum(dy);
+  ny = wave_sum(ny);
   if ((tid & 63) == 0) { red[tid >> 6][0] = dy; red[tid >> 6][1] = ny; }
   __syncthreads();
   const int64_t slot = (int64_t)b * nchunk + chunk;
@@ -114,10 +112,8 @@ __global__ void __launch_bounds__(CH_NT) chamfer_final(const float* __restrict__
     dy += pdy[(int64_t)b * nchunk + c];
     ny += pn[(int64_t)b * nchunk + c];
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    dy += __shfl_xor(dy, o, 64);
-    ny += __shfl_xor(ny, o, 64);
-  }
+  dy = wave_sum(dy);
+  ny = wave_sum(ny);
   if ((tid & 63) == 0) { red[tid >> 6][0] = dy; red[tid >> 6][1] = ny; }
   __syncthreads();
   double DY = 0.0, NY = 0.0;
@@ -162,7 +158,7 @@ __global__ void __launch_bounds__(CH_NT) chamfer_final(const float* __restrict__
     }
     gcent[(int64_t)b * P + i] = (float)(invB * g);
   }
-  for (int o = 32; o > 0; o >>= 1) cx += __shfl_xor(cx, o, 64);
+  cx = wave_sum(cx);
   if ((tid & 63) == 0) red[tid >> 6][2] = cx;
   __syncthreads();
   if (tid == 0) {

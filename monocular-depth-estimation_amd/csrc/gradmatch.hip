@@ -15,6 +15,7 @@
 // halo row/column below/right (p+s of the tile's last grid pixel is the next tile's first).
 // The backward is a gather: it also needs p-s, i.e. rows/columns -1,-2,-4,-8 above/left.
 #include "common.h"
+#include "image_reduce.h"
 #include "mdemi_ext.h"
 
 namespace mdemi {
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(GM_THREADS) void gm_fwd_kernel(const float* __restr
 }
 
 // One block: each group's partials are summed by all threads in a fixed strided order, then a
-// fixed fp64 tree through LDS (as silog_finalize).  Writes loss[0] and wk[b][k] = dL/dS_bk:
+// fixed fp64 tree through LDS (block_tree_sum, as silog_finalize).  Writes loss[0] and wk[b][k] = dL/dS_bk:
 // per batch 1 / sum_b N_bk, per image 1 / (N_bk * images used); 0 for an empty or unused scale.
 constexpr int GMF_THREADS = 256;
 __global__ __launch_bounds__(GMF_THREADS) void gm_finalize(const float* __restrict__ part, int nblk, int B, int K,
@@ -170,16 +171,7 @@ __global__ __launch_bounds__(GMF_THREADS) void gm_finalize(const float* __restri
       acc[0] += a.x; acc[1] += a.y; acc[2] += a.z; acc[3] += a.w;
       acc[4] += b.x; acc[5] += b.y; acc[6] += b.z; acc[7] += b.w;
     }
-#pragma unroll
-    for (int q = 0; q < 2 * GM_MAXK; ++q) red[q][t] = acc[q];
-    __syncthreads();
-    for (int w = GMF_THREADS / 2; w > 0; w >>= 1) {
-      if (t < w) {
-#pragma unroll
-        for (int q = 0; q < 2 * GM_MAXK; ++q) red[q][t] += red[q][t + w];
-      }
-      __syncthreads();
-    }
+    block_tree_sum(acc, red);
     if (t == 0) {
       double lg = 0.0;
       for (int k = 0; k < GM_MAXK; ++k) {

@@ -4,6 +4,7 @@
 // arithmetic, chunking and combine order, so on a given q both give the same bits.
 #pragma once
 #include "common.h"
+#include "image_reduce.h"
 #include "mdemi_ext.h"
 
 namespace mdemi {
@@ -27,17 +28,29 @@ __device__ __forceinline__ float aligned_value(float p, double s, double t, bool
   return (float)(s * (double)p + t);
 }
 
+// chunk blockIdx.x of an image's HW pixels: [p0, p1)
+__device__ __forceinline__ void met_chunk(int64_t HW, int nchunk, int64_t& p0, int64_t& p1) {
+  const int64_t per = (HW + nchunk - 1) / nchunk;
+  p0 = (int64_t)blockIdx.x * per;
+  p1 = min(HW, p0 + per);
+}
+// pixel p of a W-wide image counts: inside the crop rectangle, ground truth g in (dmin, dmax)
+__device__ __forceinline__ bool met_valid(int64_t p, int W, float g, int y0, int y1, int x0, int x1, float dmin,
+                                          float dmax) {
+  const int y = (int)(p / W), x = (int)(p % W);
+  return !(y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax));
+}
+
 template <int ALIGN, typename... AL>
 __global__ __launch_bounds__(256) void metrics_partial(const float* __restrict__ pred, const float* __restrict__ gt,
                                                        double* __restrict__ part, int H, int W, int y0, int y1, int x0,
                                                        int x1, float dmin, float dmax, int clamp_pred, int nchunk,
                                                        AL... al_pack) {
   static_assert(sizeof...(AL) == (ALIGN ? 1 : 0), "ALIGN = 1 takes one MetAlign, ALIGN = 0 nothing");
-  __shared__ float red[MET_N][4];
-  const int b = blockIdx.y, ch = blockIdx.x;
+  const int b = blockIdx.y;
   const int64_t HW = (int64_t)H * W;
-  const int64_t per = (HW + nchunk - 1) / nchunk;
-  const int64_t p0 = (int64_t)ch * per, p1 = min(HW, p0 + per);
+  int64_t p0, p1;
+  met_chunk(HW, nchunk, p0, p1);
   double s = 1.0, t = 0.0, inv_dmax = 0.0;
   bool failed = true;
   if constexpr (ALIGN != 0) {
@@ -51,18 +64,17 @@ __global__ __launch_bounds__(256) void metrics_partial(const float* __restrict__
 #pragma unroll
   for (int i = 0; i < MET_N; ++i) acc[i] = 0.f;
   for (int64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-    const int y = (int)(p / W), x = (int)(p % W);
     const float g = gt[(int64_t)b * HW + p];
+    const bool skip = !met_valid(p, W, g, y0, y1, x0, x1, dmin, dmax);
     float q;
     if constexpr (ALIGN != 0) {
       const MetAlign& al = met_align(al_pack...);
-      const bool skip = y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax);
       if (skip && !al.aligned) continue;
       q = aligned_value(pred[(int64_t)b * HW + p], s, t, failed, al.mode, inv_dmax);
       if (al.aligned) al.aligned[(int64_t)b * HW + p] = q;  // off the valid set too
       if (skip) continue;
     } else {
-      if (y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax)) continue;
+      if (skip) continue;
       q = pred[(int64_t)b * HW + p];
     }
     if (clamp_pred) q = fminf(fmaxf(q, dmin), dmax);
@@ -82,18 +94,8 @@ __global__ __launch_bounds__(256) void metrics_partial(const float* __restrict__
     acc[9] += err * err;
     acc[10] += fabsf(log10f(g) - log10f(q));
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < MET_N; ++i) {
-    const float v = wave_sum(acc[i]);
-    if (lane == 0) red[i][wid] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < MET_N) {
-    const int i = threadIdx.x;
-    part[((int64_t)b * nchunk + ch) * MET_N + i] =
-        ((double)red[i][0] + (double)red[i][1]) + ((double)red[i][2] + (double)red[i][3]);
-  }
+  // float accumulators and wave tree; only the four waves' sums are added in fp64
+  block_store_pairwise(acc, part + ((int64_t)b * nchunk + blockIdx.x) * MET_N);
 }
 
 // out rows are 10 wide, or 12 with the image's (s, t) appended when ALIGN
@@ -105,6 +107,7 @@ __global__ void metrics_final(const double* __restrict__ part, double* __restric
   if (b >= B) return;
   double s[MET_N];
   for (int i = 0; i < MET_N; ++i) s[i] = 0.0;
+  // chunk order, one thread: chunk_sums_strided is faster but changes the numbers' last bits, a change of its own
   for (int c = 0; c < nchunk; ++c)
     for (int i = 0; i < MET_N; ++i) s[i] += part[((int64_t)b * nchunk + c) * MET_N + i];
   const double n = s[0];

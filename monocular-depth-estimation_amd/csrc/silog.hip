@@ -8,6 +8,7 @@
 // sqrt(E[g^2] - 0.85 E[g]^2) * 10; unbiased=1 gives AdaBins' torch.var form.
 // HBM-bound masked two-moment reduction; partial sums are combined in fp64.
 #include "common.h"
+#include "image_reduce.h"
 
 namespace mdemi {
 
@@ -39,8 +40,8 @@ __global__ __launch_bounds__(SL_THREADS) void silog_partial(const float* __restr
 }
 
 // stats[g] = {n, mean, D, sqrt(D)}; loss = mean_g alpha*sqrt(D_g).  One block: the
-// partials of a group are summed by all threads in a fixed strided order, then a
-// fixed fp64 tree through LDS (deterministic, no serial pass over B x nblk partials).
+// partials of a group are summed by all threads in a fixed strided order, then a fixed
+// fp64 tree through LDS (block_tree_sum: deterministic, no serial pass over B x nblk partials).
 constexpr int SLF_THREADS = 256;
 __global__ __launch_bounds__(SLF_THREADS) void silog_finalize(const float* __restrict__ part, int nblk, int B,
                                                               int per_image, int unbiased, float alpha, float beta,
@@ -53,21 +54,14 @@ __global__ __launch_bounds__(SLF_THREADS) void silog_finalize(const float* __res
   for (int g = 0; g < G; ++g) {
     const int b0 = per_image ? g : 0, b1 = per_image ? g + 1 : B;
     const int64_t j0 = (int64_t)b0 * nblk, j1 = (int64_t)b1 * nblk;
-    double n = 0, s1 = 0, s2 = 0;
+    double acc[3] = {0.0, 0.0, 0.0};  // n, s1, s2
     for (int64_t j = j0 + t; j < j1; j += SLF_THREADS) {
       const float* o = part + j * 3;
-      n += o[0]; s1 += o[1]; s2 += o[2];
+      acc[0] += o[0]; acc[1] += o[1]; acc[2] += o[2];
     }
-    red[0][t] = n; red[1][t] = s1; red[2][t] = s2;
-    __syncthreads();
-    for (int w = SLF_THREADS / 2; w > 0; w >>= 1) {
-      if (t < w) {
-        red[0][t] += red[0][t + w]; red[1][t] += red[1][t + w]; red[2][t] += red[2][t + w];
-      }
-      __syncthreads();
-    }
+    block_tree_sum(acc, red);
     if (t == 0) {
-      n = red[0][0]; s1 = red[1][0]; s2 = red[2][0];
+      const double n = red[0][0], s1 = red[1][0], s2 = red[2][0];
       double mean = n > 0 ? s1 / n : 0.0, D = 0.0;
       if (n > 0) {
         const double var = unbiased ? (n > 1 ? (s2 - n * mean * mean) / (n - 1) : 0.0) : (s2 / n - mean * mean);

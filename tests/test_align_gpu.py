@@ -196,6 +196,25 @@ def test_deterministic_and_layout_independent(mf, mode):
     assert all(torch.equal(a, b) for a, b in zip(want, all_bits(off_p, off_g)))
 
 
+def test_median_workspace_aligned_to_8_bytes_only(mf):
+    """mdemi_depth_align asks for an 8-byte-aligned workspace and no more: a workspace at 8 mod 16
+    (the select's tables then sit at 8 mod 16 too) gives the bits of mf.depth_align's."""
+    from mdemi import _lib as L
+    lib = L.load()
+    shape = A.SHAPES[1]
+    pred, gt = A.make_inputs(*shape)
+    B, H, W = shape[:3]
+    p, g = dev(pred)[:, None], dev(gt)[:, None]
+    rect = A.rect_of(H, W)
+    want = mf.depth_align(p, g, rect, A.DMIN, A.DMAX, "median")
+    ws = torch.zeros(lib.mdemi_depth_align_workspace_size(B, H, W, L.ALIGN_MEDIAN) + 16, device=DEV, dtype=torch.uint8)
+    assert ws.data_ptr() % 16 == 0
+    coef = torch.empty(B, 4, device=DEV, dtype=torch.float64)
+    L.check(lib.mdemi_depth_align(p.data_ptr(), g.data_ptr(), B, H, W, *rect, A.DMIN, A.DMAX, L.ALIGN_MEDIAN,
+                                  coef.data_ptr(), ws.data_ptr() + 8, L.stream()), "depth_align")
+    assert torch.equal(bits(coef), bits(want))
+
+
 def test_default_is_untouched(mf):
     """Without align, depth_metrics returns its ten columns and tcompute_errors_gpu its nine keys,
     with the values of the unaligned prediction; "none" is the same as no key."""

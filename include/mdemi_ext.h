@@ -523,6 +523,55 @@ int mdemi_ssi_fwd(const float* pred, const float* gt, float* loss, double* coef,
 int mdemi_ssi_bwd(const float* pred, const float* gt, const double* coef, const float* dloss, float* dpred, int32_t B,
                   int32_t H, int32_t W, float min_depth, int32_t space, void* stream);
 
+/* ------------------------------------------------------------------------ */
+/* Tiled inference (cfg eval.tile / tile_overlap / tile_align; this          */
+/* framework's own definition, DESIGN.md 1c -- no reference parity).  The    */
+/* plan is two ascending host arrays of tile origins, ys [ny] and xs [nx],   */
+/* ny, nx in 1..MDEMI_TILE_MAX_AXIS, for tiles of th x tw inside the H x W   */
+/* image (H * W < 2^31); they are copied into the kernel arguments, so every */
+/* call can be captured.  Tile k = iy * nx + ix, T = ny * nx; image b's tile */
+/* k sits at index b * T + k.  oy, ox in [0, th), [0, tw) are the overlaps   */
+/* the ramps are built from: wy(u) = min(u + 1, th - u, max(1, oy)) on row u */
+/* of a tile, wx the same, w = wy * wx (an exact integer in fp64).           */
+/*   mdemi_tile_extract: out [B*T][C][th][tw] = the tiles of img             */
+/*     [B][C][H][W], bit for bit, one launch; T * C <= 65535.  16-byte       */
+/*     accesses where the pointer, W, tw and the tile's x origin allow.      */
+/*   mdemi_tile_blend: out [B][H][W] = (float)(sum_k w_k q_k / sum_k w_k)    */
+/*     over the tiles that cover the pixel, in ascending k, every operation  */
+/*     in fp64, rounded once; one launch, a gather without atomics.  The     */
+/*     tiles must cover the image (first origin 0, last H - th, no gap).     */
+/*     tiles [B*T][th][tw] holds the predictions p.  mode MDEMI_TILE_NONE:   */
+/*     q = p, coef may be NULL.  MDEMI_ALIGN_LSTSQ: q = s p + t with         */
+/*     (s, t) = coef[b][k].  MDEMI_ALIGN_LSTSQ_DISP: q = s / p + t (fp64     */
+/*     reciprocal) and out = (float)(1 / max(blend, 1 / max_depth)).  NaN    */
+/*     and inf propagate (the max too keeps a NaN).                          */
+/*   mdemi_tile_align: coef [B][T][4] = s, t, n, status (fp64).  Tile 0 is   */
+/*     the anchor (1, 0, 0, 0).  For k = 1 .. T-1 in order, over the pixels  */
+/*     of tile k that some tile j < k covers: x = p_k (LSTSQ) or 1 / p_k     */
+/*     (LSTSQ_DISP), y = the fp64 blend (formula above) of the q_j, j < k;   */
+/*     pairs with a non-finite x or y, and under LSTSQ_DISP with p_k <= 0,   */
+/*     are left out; (s, t) minimise sum (s x + t - y)^2 (the LSTSQ solve of */
+/*     mdemi_depth_align).  A tile fails -- status 1, s = 1, t = 0 -- when   */
+/*     n < 2, det is not finite and > 0, or s is not > 0.  An axis with      */
+/*     several tiles needs an overlap > 0.  1 + 2 (T - 1) launches enqueued  */
+/*     by the call: the anchor rows, then per tile one statistics kernel     */
+/*     (per-chunk fp64 partials) and one one-wave-per-image solve.           */
+/* None synchronises or allocates; every sum is fp64 in a fixed order: two   */
+/* runs give the same bits.  workspace: mdemi_tile_align_workspace_size      */
+/* bytes, 8-byte aligned.  B is 1..65535.                                    */
+/* ------------------------------------------------------------------------ */
+#define MDEMI_TILE_MAX_AXIS 32
+#define MDEMI_TILE_NONE 0
+int mdemi_tile_extract(const float* img, float* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t th,
+                       int32_t tw, const int32_t* ys, int32_t ny, const int32_t* xs, int32_t nx, void* stream);
+size_t mdemi_tile_align_workspace_size(int32_t B, int32_t th, int32_t tw);
+int mdemi_tile_align(const float* tiles, int32_t B, int32_t H, int32_t W, int32_t th, int32_t tw, int32_t oy,
+                     int32_t ox, const int32_t* ys, int32_t ny, const int32_t* xs, int32_t nx, int32_t mode,
+                     double* coef, void* workspace, void* stream);
+int mdemi_tile_blend(const float* tiles, const double* coef, int32_t B, int32_t H, int32_t W, int32_t th, int32_t tw,
+                     int32_t oy, int32_t ox, const int32_t* ys, int32_t ny, const int32_t* xs, int32_t nx,
+                     int32_t mode, float max_depth, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

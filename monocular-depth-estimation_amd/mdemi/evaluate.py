@@ -17,6 +17,8 @@ of the driver itself is unpinned; each helper is pinned by its own tests):
              pred clamped into [min_depth_eval, max_depth_eval]
   eval.align "median" / "lstsq" / "lstsq_disp" (this framework's own key,
   DESIGN.md 1c): pred is first aligned per image to its ground truth
+  eval.tile (this framework's own key): pred comes from a
+  TiledPredictor -- the model run on overlapping tiles, the tiles blended
 
 Every step is a libmdemi launch (flip: mdemi_flip_w / mdemi_flip_avg_w;
 resize: mdemi_bilinear_*; metrics: mdemi_depth_metrics, or mdemi_depth_align +
@@ -31,7 +33,7 @@ from .utils.common_utils import RunningAverageDict
 from .utils.depth_utils import tcompute_errors_gpu
 from .utils.dist_utils import all_reduce_dict
 
-__all__ = ["predict_depth", "evaluate_batch", "evaluate", "GraphedPredictor"]
+__all__ = ["predict_depth", "evaluate_batch", "evaluate", "GraphedPredictor", "TiledPredictor"]
 
 
 def _depth_of(out):
@@ -55,8 +57,8 @@ def predict_depth(model, img, flip_eval=False, size=None):
 
 def evaluate_batch(model, img, gt, eval_opt, data_type):
     """Per-image metric dicts (the reference's keys) for one batch.  `model` may be a
-    GraphedPredictor (its capture fixes flip_eval)."""
-    if isinstance(model, GraphedPredictor):
+    GraphedPredictor (its capture fixes flip_eval) or a TiledPredictor."""
+    if isinstance(model, (GraphedPredictor, TiledPredictor)):
         pred = model(img)
         if tuple(pred.shape[-2:]) != tuple(gt.shape[-2:]):
             B, _, h, w = pred.shape
@@ -99,6 +101,92 @@ class GraphedPredictor:
         self.static_in.copy_(img)
         self.graph.replay()
         return self.static_out.clone()
+
+
+class TiledPredictor:
+    """Sliding-window inference (cfg eval.tile): callable like predict_depth,
+    (B,3,H,W) -> (B,1,H,W) at the image's size, whatever that is.  The image is cut into tiles of
+    `tile` overlapping by `overlap` (functional.tile_plan / tile_extract, one launch), the tiles go
+    through the model `tile_batch` at a time (all at once when None), and functional.tile_merge
+    blends the per-tile predictions with a ramp over the overlaps -- with align "lstsq" /
+    "lstsq_disp" after fitting each tile's scale and shift to the tiles before it, for models whose
+    depth is only defined up to those (max_depth bounds the "lstsq_disp" result).  An axis on
+    which the image is no larger than the tile has one tile, clipped to the image.
+
+    `model` is an nn.Module in eval mode or a GraphedPredictor captured at (tile_batch, 3, th, tw):
+    its capture fixes flip_eval and tile_batch, a last chunk that is short is filled by repeating
+    its final tile and the filling dropped, so images of every size replay the one graph.
+    Half-resolution heads are resized per tile to the tile (bilinear, align_corners=True) before
+    the merge.  `coef` keeps the last call's (B,T,4) fit rows (None under align "none")."""
+
+    def __init__(self, model, tile, overlap, align="none", max_depth=None, flip_eval=False, tile_batch=None):
+        from .utils.depth_utils import _pair, check_tile_align
+        self.model, self.align, self.max_depth = model, check_tile_align(align, "align"), max_depth
+        self.tile, self.overlap = _pair(tile, "tile", 1), _pair(overlap, "overlap", 0)
+        if self.align == "lstsq_disp" and not (max_depth is not None and max_depth > 0):
+            raise ValueError(f"align 'lstsq_disp' needs max_depth > 0, got {max_depth!r}")
+        self.graphed = isinstance(model, GraphedPredictor)
+        if self.graphed:
+            captured = tuple(model.static_in.shape)
+            if tile_batch is None:
+                tile_batch = captured[0]
+            if captured != (tile_batch, 3, *self.tile):
+                raise ValueError(f"TiledPredictor: the GraphedPredictor captured {captured}, the tiles come as "
+                                 f"{(tile_batch, 3, *self.tile)}")
+            flip_eval = model.flip_eval
+        if tile_batch is not None and (isinstance(tile_batch, bool) or not isinstance(tile_batch, int) or tile_batch < 1):
+            raise ValueError(f"tile_batch must be a positive integer, got {tile_batch!r}")
+        self.flip_eval, self.tile_batch = bool(flip_eval), tile_batch
+        self.coef, self._plans = None, {}
+
+    # evaluate() switches its model to eval mode and back
+    @property
+    def training(self):
+        return False if self.graphed else self.model.training
+
+    def eval(self):
+        return self.train(False)
+
+    def train(self, mode=True):
+        if not self.graphed:
+            self.model.train(mode)
+        return self
+
+    def plan(self, H, W):
+        """The tile plan of an H x W image; the overlap is dropped on an axis that has one tile."""
+        p = self._plans.get((H, W))
+        if p is None:
+            overlap = tuple(0 if n <= t else o for n, t, o in zip((H, W), self.tile, self.overlap))
+            p = self._plans[(H, W)] = mf.tile_plan(H, W, self.tile, overlap)
+        return p
+
+    def __call__(self, img):
+        if img.dim() != 4:
+            raise ValueError(f"TiledPredictor: img must be (B,3,H,W), got {tuple(img.shape)}")
+        H, W = img.shape[-2:]
+        plan = self.plan(H, W)
+        with torch.no_grad():
+            tiles = mf.tile_extract(img.detach(), plan)
+            n_all = tiles.shape[0]
+            step = self.tile_batch or n_all
+            preds = []
+            for i in range(0, n_all, step):
+                chunk = tiles[i:i + step]
+                n = chunk.shape[0]
+                if self.graphed:
+                    if n < step:  # the captured shape: repeat the final tile, drop its predictions below
+                        chunk = torch.cat([chunk, chunk[-1:].expand(step - n, -1, -1, -1)])
+                    pred = self.model(chunk)
+                    if tuple(pred.shape[-2:]) != plan.tile:
+                        h, w = pred.shape[-2:]
+                        pred = mf.interpolate_bilinear(pred.reshape(step, h, w, 1), size=plan.tile,
+                                                       align_corners=True).reshape(step, 1, *plan.tile)
+                else:
+                    pred = predict_depth(self.model, chunk, self.flip_eval, size=plan.tile)
+                preds.append(pred[:n])
+            pred = preds[0] if len(preds) == 1 else torch.cat(preds)
+            depth, self.coef = mf.tile_merge(pred, plan, (H, W), self.align, self.max_depth)
+        return depth
 
 
 def evaluate(model, batches, eval_opt, data_type, weight_by_count=False):

@@ -2313,6 +2313,82 @@ def depth_export(pred, size=None, vmin=10, vmax=1000, lut=None, png_scale=None, 
     return out
 
 
+TILE_CODES = {"none": L.TILE_NONE, "lstsq": L.ALIGN_LSTSQ, "lstsq_disp": L.ALIGN_LSTSQ_DISP}
+
+
+def tile_plan(H, W, tile, overlap=0):
+    """The sliding-window plan of an H x W image (utils.depth_utils.tile_plan); host only."""
+    from .utils.depth_utils import tile_plan as plan_of
+    return plan_of(H, W, tile, overlap)
+
+
+def _plan_args(plan):
+    ys = (ctypes.c_int32 * len(plan.ys))(*plan.ys)
+    xs = (ctypes.c_int32 * len(plan.xs))(*plan.xs)
+    return ys, len(plan.ys), xs, len(plan.xs)
+
+
+def _no_grad_input(t, who):
+    if t.requires_grad:
+        raise ValueError(f"{who} has no backward: the input requires grad (detach it, or run under torch.no_grad() "
+                         "from a tensor that does not)")
+
+
+def tile_extract(img, plan):
+    """The plan's tiles of img (B,C,H,W) -> (B*T,C,th,tw), image b's tile k at b*T + k: a bit-exact
+    copy in one launch (mdemi_tile_extract).  No autograd; does not synchronise."""
+    _require_cuda(img)
+    _no_grad_input(img, "tile_extract")
+    if img.dim() != 4 or tuple(img.shape[-2:]) != tuple(plan.size):
+        raise ValueError(f"tile_extract: img must be (B,C,{plan.size[0]},{plan.size[1]}), got {tuple(img.shape)}")
+    img = _c(img)
+    B, C, H, W = img.shape
+    (th, tw), T = plan.tile, len(plan.ys) * len(plan.xs)
+    out = torch.empty(B * T, C, th, tw, device=img.device, dtype=torch.float32)
+    if out.numel():
+        L.call("mdemi_tile_extract", img.data_ptr(), out.data_ptr(), B, C, H, W, th, tw, *_plan_args(plan), L.stream())
+    return out
+
+
+def tile_merge(tile_pred, plan, size, align="none", max_depth=None):
+    """Per-tile predictions (B*T,1,th,tw) -> (depth (B,1,H,W), coef (B,T,4) fp64 or None) for the
+    plan of an image of ``size``.  align "none": the ramp-weighted mean of the
+    covering tiles in fp64, rounded once (mdemi_tile_blend, one launch).  "lstsq" / "lstsq_disp",
+    for affine-invariant predictions: tile 0 anchors and each later tile is first fitted a scale
+    and shift -- in depth or in inverse depth -- to the blend of the tiles before it over the
+    pixels they share (mdemi_tile_align, 1 + 2(T-1) launches); coef rows are s, t, n, status,
+    status 1 a tile that could not be fitted and keeps s = 1, t = 0.  "lstsq_disp" blends in
+    inverse depth and returns 1 / max(blend, 1 / max_depth).  No autograd; does not synchronise."""
+    from .utils.depth_utils import check_tile_merge
+    check_tile_merge(plan, align, max_depth)
+    _require_cuda(tile_pred)
+    _no_grad_input(tile_pred, "tile_merge")
+    if tuple(size) != tuple(plan.size):
+        raise ValueError(f"tile_merge: the plan is for a {plan.size} image, not {tuple(size)}")
+    (th, tw), (H, W), (oy, ox) = plan.tile, plan.size, plan.overlap
+    T = len(plan.ys) * len(plan.xs)
+    if tile_pred.dim() == 4 and tile_pred.shape[1] == 1:
+        tile_pred = tile_pred[:, 0]
+    if tile_pred.dim() != 3 or tuple(tile_pred.shape[1:]) != (th, tw) or tile_pred.shape[0] % T or not tile_pred.shape[0]:
+        raise ValueError(f"tile_merge: tile_pred must be (B*{T},1,{th},{tw}), got {tuple(tile_pred.shape)}")
+    tile_pred = _c(tile_pred)
+    B = tile_pred.shape[0] // T
+    dev = tile_pred.device
+    code = TILE_CODES[align]
+    lib = L.load()
+    pa = _plan_args(plan)
+    coef = None
+    if align != "none":
+        coef = torch.empty(B, T, 4, device=dev, dtype=torch.float64)
+        ws = _ws(lib.mdemi_tile_align_workspace_size(B, th, tw), dev, slot=3)
+        L.check(lib.mdemi_tile_align(tile_pred.data_ptr(), B, H, W, th, tw, oy, ox, *pa, code, coef.data_ptr(),
+                                     ws.data_ptr(), L.stream()), "tile_align")
+    out = torch.empty(B, 1, H, W, device=dev, dtype=torch.float32)
+    L.check(lib.mdemi_tile_blend(tile_pred.data_ptr(), L.ptr(coef), B, H, W, th, tw, oy, ox, *pa, code,
+                                 float(max_depth or 0.0), out.data_ptr(), L.stream()), "tile_blend")
+    return out, coef
+
+
 class _BinsChamferFn(torch.autograd.Function):
     """Bin-centre chamfer loss (upstream AdaBins BinsChamferLoss over pytorch3d chamfer_distance
     defaults; the reference's loss module is absent -- parity unpinned): batch mean of

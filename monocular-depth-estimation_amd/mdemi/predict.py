@@ -1,7 +1,8 @@
 """Prediction export: image files -> depth PNGs and colour maps.
 
   python -m mdemi.predict --config <json> --checkpoint <file> --data-path <dir> \
-         --mode test|benchmark --out <dir> [--graph] [--cmap jet] [--no-colour] [--no-raw16]
+         --mode test|benchmark --out <dir> [--graph] [--cmap jet] [--no-colour] [--no-raw16] \
+         [--tile H W [--tile-overlap N | OY OX] [--tile-align none|lstsq|lstsq_disp]]
 
 Per batch: the model's prediction (``evaluate.predict_depth`` or a
 ``GraphedPredictor``), then ONE ``mdemi_depth_export`` launch that resizes the
@@ -29,7 +30,7 @@ import numpy as np
 import torch
 
 from . import functional as mf
-from .evaluate import GraphedPredictor, predict_depth
+from .evaluate import GraphedPredictor, TiledPredictor, predict_depth
 
 __all__ = ["export_predictions", "png_scale_of", "main"]
 
@@ -123,7 +124,8 @@ def export_predictions(model, batches: Iterable, out_dir: str, data_type: str, e
         ``collate_fn=collate_raw``) yields -- a dict with ``image`` and ``image_path`` -- or plain
         ``(img, paths)`` pairs; ``img`` is the normalised (B,3,H,W) fp32 batch or the decoded
         (B,H,W,3) uint8 frames (those go through the test-mode GpuSampleTransform).
-    model: an nn.Module in eval mode or a GraphedPredictor (its capture fixes flip_eval).
+    model: an nn.Module in eval mode, a GraphedPredictor (its capture fixes flip_eval) or a
+        TiledPredictor (eval.tile: sliding-window inference, each file at its image's size).
     eval_opt: the config's ``eval`` block: min_depth_eval / max_depth_eval bound the colour map,
         flip_eval averages in the flipped pass.
     Predictions are written at the resolution the dataset yields (the KB-cropped 352x1216
@@ -136,8 +138,8 @@ def export_predictions(model, batches: Iterable, out_dir: str, data_type: str, e
     vmin, vmax = float(eval_opt.get("min_depth_eval", 1e-3)), float(eval_opt.get("max_depth_eval", 10.0))
     flip = bool(eval_opt.get("flip_eval", False))
     dev = torch.device("cuda", torch.cuda.current_device())
-    graphed = isinstance(model, GraphedPredictor)
-    was_training = (not graphed) and model.training
+    graphed = isinstance(model, (GraphedPredictor, TiledPredictor))  # called with the image alone
+    was_training = (not isinstance(model, GraphedPredictor)) and model.training
     if was_training:
         model.eval()
     sets, written, transforms = (_HostSet(), _HostSet()), [], {}
@@ -197,6 +199,14 @@ def main(argv=None) -> List[str]:
     ap.add_argument("--graph", action="store_true", help="replay the prediction as a captured hipGraph")
     ap.add_argument("--ema", action="store_true", help="predict with the checkpoint's averaged weights "
                                                        "(ema_state_dict, written under train.ema_decay)")
+    ap.add_argument("--tile", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="override the config's eval.tile: predict on overlapping H x W tiles of each image, blended "
+                         "back to its size; with --graph one capture at the tile serves images of every size")
+    ap.add_argument("--tile-overlap", type=int, nargs="+", default=None, metavar="N",
+                    help="override eval.tile_overlap: one overlap for both axes, or OY OX (default: a quarter of "
+                         "the tile)")
+    ap.add_argument("--tile-align", default=None, choices=["none", "lstsq", "lstsq_disp"],
+                    help="override eval.tile_align: fit each tile's scale and shift to the tiles before it")
     ap.add_argument("--cmap", default="jet")
     ap.add_argument("--no-colour", action="store_true")
     ap.add_argument("--no-raw16", action="store_true")
@@ -208,6 +218,10 @@ def main(argv=None) -> List[str]:
     from .train.builder import build_model
     with open(args.config, "r", encoding="utf-8") as f:
         opt = json.load(f)
+    from .run import tile_overrides
+    from .train.builder import eval_tile
+    tile_overrides(opt, args)
+    tile = eval_tile(opt)  # a bad eval.tile / tile_overlap / tile_align / tile_batch fails here, before any GPU work
     eval_opt = dict(opt.get("eval", {}))
     data_type = opt["dataset"]["data_type"].upper()
     if not torch.cuda.is_available():
@@ -227,7 +241,14 @@ def main(argv=None) -> List[str]:
     transforms = {}
     it = (_split(b, data_type, dev, transforms) for b in loader)
     rest = (args.out, data_type, eval_opt, not args.no_colour, not args.no_raw16, args.cmap, args.workers)
-    if not args.graph:
+    flip = bool(eval_opt.get("flip_eval", False))
+    if tile is not None:
+        inner = model
+        if args.graph:  # one capture at the tile: images of every size replay it
+            tile["tile_batch"] = tile["tile_batch"] or bs
+            inner = GraphedPredictor(model, torch.zeros(tile["tile_batch"], 3, *tile["tile"], device=dev), flip)
+        written = export_predictions(TiledPredictor(inner, flip_eval=flip, **tile), it, *rest)
+    elif not args.graph:
         written = export_predictions(model, it, *rest)
     else:
         written, first = [], next(it, None)

@@ -50,6 +50,14 @@ def _args(argv):
                     help="override the config's eval.align: align each prediction to its ground truth before the "
                          "metrics (validation and --test) by median scaling, or by least-squares scale and shift "
                          "in depth (lstsq) or in inverse depth (lstsq_disp)")
+    ap.add_argument("--tile", type=int, nargs=2, default=None, metavar=("H", "W"),
+                    help="override the config's eval.tile: validate / test on overlapping H x W tiles of each "
+                         "image, blended back to its size")
+    ap.add_argument("--tile-overlap", type=int, nargs="+", default=None, metavar="N",
+                    help="override eval.tile_overlap: one overlap for both axes, or OY OX (default: a quarter of "
+                         "the tile)")
+    ap.add_argument("--tile-align", default=None, choices=["none", "lstsq", "lstsq_disp"],
+                    help="override eval.tile_align: fit each tile's scale and shift to the tiles before it")
     ap.add_argument("--ema", action="store_true",
                     help="with --test: evaluate the checkpoint's averaged weights (ema_state_dict)")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many optimizer steps (in all)")
@@ -68,7 +76,21 @@ def _override(opt, args):
         opt.setdefault("loss", {})["ssi_weight"] = args.ssi_weight
     if args.align is not None:
         opt.setdefault("eval", {})["align"] = args.align
+    tile_overrides(opt, args)
     return opt
+
+
+def tile_overrides(opt, args):
+    """--tile / --tile-overlap / --tile-align written over the config's eval.tile* keys."""
+    if args.tile is not None:
+        opt.setdefault("eval", {})["tile"] = list(args.tile)
+    if args.tile_overlap is not None:
+        if len(args.tile_overlap) > 2:
+            raise SystemExit("--tile-overlap takes one value or two (OY OX)")
+        o = args.tile_overlap
+        opt.setdefault("eval", {})["tile_overlap"] = o[0] if len(o) == 1 else list(o)
+    if args.tile_align is not None:
+        opt.setdefault("eval", {})["tile_align"] = args.tile_align
 
 
 def _dataset(opt, mode, list_root):
@@ -117,13 +139,14 @@ def main(argv=None) -> int:
 
     # 1. the config
     opt = _override(parse(args.opt, write_option=rank == 0 and not args.test), args)
-    from .train.builder import eval_align, grad_match_config, nonfinite_policy, ssi_config
+    from .train.builder import eval_align, eval_tile, grad_match_config, nonfinite_policy, ssi_config
     from .train.ema import ema_config
     nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
     ema_config(opt)  # and so does a bad train.ema_decay / ema_warmup / ema_validate
     grad_match_config(opt)  # and a bad loss.grad_weight / grad_scales
     ssi_config(opt)  # and a bad loss.ssi_weight / ssi_space / ssi_trim / ssi_norm
     align = eval_align(opt)  # and a bad eval.align
+    tile = eval_tile(opt)  # and a bad eval.tile / tile_overlap / tile_align / tile_batch
     if args.ema and not args.test:
         raise SystemExit("mdemi.run --ema selects the weights --test evaluates; to train with averaged weights set "
                          "train.ema_decay (or --ema-decay)")
@@ -183,20 +206,28 @@ def main(argv=None) -> int:
             img, gt, _ = test_tf(b["image"], b["depth"])
             yield img, gt
 
-    from .evaluate import evaluate
+    from .evaluate import TiledPredictor, evaluate
+
+    def predictor(model):  # eval.tile: the model behind a sliding window
+        if tile is None:
+            return model
+        return TiledPredictor(model, flip_eval=bool(eval_opt.get("flip_eval", False)), **tile)
+
     try:
         if args.test:
             from .predict import _load_weights
             model = build_model(opt, drop_path=0.0)
             _load_weights(model, ck_path, ema=args.ema)
             model.to(dev).eval()
-            metrics = {k: float(v) for k, v in evaluate(model, test_batches(), eval_opt, data_type,
+            metrics = {k: float(v) for k, v in evaluate(predictor(model), test_batches(), eval_opt, data_type,
                                                         weight_by_count=True).items()}
             rec = {"type": "test", "checkpoint": ck_path, **metrics}
             if args.ema:
                 rec["weights"] = "ema"
             if align != "none":
                 rec["align"] = align
+            if tile is not None:
+                rec.update(tile=list(tile["tile"]), tile_align=tile["align"])
             if rank == 0:
                 os.makedirs(out_dir, exist_ok=True)
                 with open(os.path.join(out_dir, "log.jsonl"), "a", encoding="utf-8") as f:
@@ -221,8 +252,8 @@ def main(argv=None) -> int:
                                start_epoch=start_epoch, start_step=start_step)
 
         def validate(model=None):  # fit names the model when it validates averaged weights
-            return evaluate(model if model is not None else trainer.model, test_batches(), eval_opt, data_type,
-                            weight_by_count=True)
+            return evaluate(predictor(model if model is not None else trainer.model), test_batches(), eval_opt,
+                            data_type, weight_by_count=True)
 
         return fit(trainer, batches, validate, opt, out_dir, steps_per_epoch=spe, start_epoch=start_epoch,
                    start_step=start_step, max_steps=args.max_steps, rank=rank, world=world, best=best,

@@ -239,6 +239,38 @@ def eval_align(opt):
     return check_align_mode(opt.get("eval", {}).get("align", "none"))
 
 
+TILE_KEYS = ("tile", "tile_overlap", "tile_align", "tile_batch")
+
+
+def eval_tile(opt):
+    """eval.tile / tile_overlap / tile_align / tile_batch, validated: None when eval.tile is absent
+    (the other three must then be absent too), else the TiledPredictor arguments {"tile": (h, w),
+    "overlap": (oy, ox) (default: a quarter of the tile), "align": "none" | "lstsq" | "lstsq_disp",
+    "tile_batch": n | None, "max_depth": eval.max_depth_eval}."""
+    from ..utils.depth_utils import _pair, check_tile_align
+    ev = opt.get("eval", {})
+    if ev.get("tile") is None:
+        extra = [k for k in TILE_KEYS[1:] if k in ev]
+        if extra:
+            raise ValueError(f"eval.{extra[0]} is set but eval.tile is not: tiled inference needs eval.tile: [h, w]")
+        return None
+    tile = ev["tile"]
+    if not isinstance(tile, (list, tuple)):
+        raise ValueError(f"eval.tile must be a list [h, w] of two positive integers, got {tile!r}")
+    th, tw = _pair(tile, "eval.tile", 1)
+    oy, ox = _pair(ev["tile_overlap"], "eval.tile_overlap", 0) if "tile_overlap" in ev else (th // 4, tw // 4)
+    if oy >= th or ox >= tw:
+        raise ValueError(f"eval.tile_overlap {[oy, ox]} must be smaller than eval.tile {[th, tw]}")
+    align = check_tile_align(ev.get("tile_align", "none"))
+    batch = ev.get("tile_batch")
+    if batch is not None and (isinstance(batch, bool) or not isinstance(batch, int) or batch < 1):
+        raise ValueError(f"eval.tile_batch must be a positive integer, got {batch!r}")
+    max_depth = ev.get("max_depth_eval")
+    if align == "lstsq_disp" and not (isinstance(max_depth, (int, float)) and max_depth > 0):
+        raise ValueError(f"eval.tile_align 'lstsq_disp' needs eval.max_depth_eval > 0, got {max_depth!r}")
+    return {"tile": (th, tw), "overlap": (oy, ox), "align": align, "tile_batch": batch, "max_depth": max_depth}
+
+
 def build_optimizer(model, opt, capturable=False):
     o = opt.get("optimizer", {})
     betas = tuple(float(b) for b in o.get("betas", (0.9, 0.999)))

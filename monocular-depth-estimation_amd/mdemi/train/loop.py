@@ -33,7 +33,7 @@ import torch
 
 from .. import _lib as L
 from ..utils.dist_utils import all_reduce_dict
-from .builder import eval_align, nonfinite_policy, optimizer_steps_per_epoch
+from .builder import eval_align, eval_tile, nonfinite_policy, optimizer_steps_per_epoch
 from .ema import ema_config
 from .telemetry import NonFiniteStep
 
@@ -153,7 +153,8 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     is chosen on its abs_rel -- and, under train.ema_validate "both", on trainer.model too, for
     a second record with "weights": "model".  With eval.align other than "none" the caller's
     validate() reports aligned metrics; the record then carries "align": MODE and best.pth is
-    chosen on the aligned abs_rel.  telemetry defaults to
+    chosen on the aligned abs_rel.  With eval.tile the caller's validate() predicts in tiles and the
+    record carries "tile": [h, w] and "tile_align".  telemetry defaults to
     trainer.telemetry.  ``best`` is (abs_rel, epoch, iter) of the best checkpoint so far
     (a resumed run).  Rank 0 writes out_dir/log.jsonl -- {"type": "train", ...} every
     train.print_freq steps, {"type": "valid", ...} per validation -- and latest.pth /
@@ -182,6 +183,7 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
 
     policy, max_skips = nonfinite_policy(opt)
     align = eval_align(opt)
+    tile = eval_tile(opt)
     skip_mode = policy == "skip"
     guard = getattr(trainer.optimizer, "skipped_steps", None) if skip_mode else None
     if skip_mode and (guard is None or not getattr(trainer.optimizer, "skip_nonfinite", True)):
@@ -315,6 +317,10 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
             rec["align"] = align
             if raw is not None:
                 raw["align"] = align
+        if tile is not None:  # and those of predictions blended from tiles
+            for r in (rec, raw):
+                if r is not None:
+                    r.update(tile=list(tile["tile"]), tile_align=tile["align"])
         if ema is not None:
             rec["weights"] = "ema"
             if raw is not None:  # for the record only: best.pth is chosen on the averaged weights

@@ -6,14 +6,22 @@ the 9 metrics for a whole batch in one libmdemi launch pair
 (mdemi_depth_metrics: per-image fixed-order sums, fp64 finalize).  cfg eval.align
 aligns each prediction to its ground truth first (median scaling, or least-squares scale and
 shift in depth or in inverse depth): on the GPU inside `tcompute_errors_gpu`
-(mdemi_depth_align + mdemi_depth_metrics_aligned), on the CPU with `align_depth`."""
+(mdemi_depth_align + mdemi_depth_metrics_aligned), on the CPU with `align_depth`.  cfg eval.tile
+predicts in overlapping tiles: `tile_plan` lays them out and `merge_tiles` is the CPU counterpart
+of the GPU merge (mdemi.functional.tile_merge)."""
+from collections import namedtuple
+
 import numpy as np
 
 __all__ = ["cal_eval_mask", "tcompute_errors", "eval_crop_rect", "tcompute_errors_gpu", "METRICS", "ALIGN_MODES",
-           "check_align_mode", "align_depth"]
+           "check_align_mode", "align_depth", "TILE_ALIGN_MODES", "TILE_MAX_AXIS", "TilePlan", "check_tile_align",
+           "tile_plan", "tile_weights", "check_tile_merge", "merge_tiles"]
 
 METRICS = ("a1", "a2", "a3", "abs_rel", "sq_rel", "rmse", "rmse_log", "silog", "log_10")
 ALIGN_MODES = ("none", "median", "lstsq", "lstsq_disp")
+TILE_ALIGN_MODES = ("none", "lstsq", "lstsq_disp")
+TILE_MAX_AXIS = 32  # MDEMI_TILE_MAX_AXIS
+TilePlan = namedtuple("TilePlan", "ys xs tile overlap size")
 
 
 def check_align_mode(mode, what="eval.align"):
@@ -86,6 +94,127 @@ def align_depth(gt: np.ndarray, pred: np.ndarray, mode: str, max_depth: float):
         if mode == "lstsq_disp":
             return 1.0 / np.maximum(s * x + t, 1.0 / max_depth), s, t
         return s * p + t, s, t
+
+
+def check_tile_align(mode, what="eval.tile_align"):
+    if not isinstance(mode, str) or mode not in TILE_ALIGN_MODES:
+        raise ValueError(f"{what} must be one of {TILE_ALIGN_MODES}, got {mode!r}")
+    return mode
+
+
+def _pair(v, what, least):
+    """An int, or a list of two, >= least -> (a, b); booleans and floats are refused."""
+    vs = (v, v) if isinstance(v, int) else tuple(v) if isinstance(v, (list, tuple)) else None
+    if (vs is None or len(vs) != 2
+            or any(isinstance(a, bool) or not isinstance(a, (int, np.integer)) or a < least for a in vs)):
+        raise ValueError(f"{what} must be an integer >= {least} or a list of two, got {v!r}")
+    return int(vs[0]), int(vs[1])
+
+
+def _axis_plan(size, tile, overlap, axis):
+    tile = min(tile, size)
+    if not 0 <= overlap < tile:
+        raise ValueError(f"tile_plan: the {axis} overlap {overlap} must be in [0, {tile}), the tile clipped to the image")
+    if size == tile:
+        return tile, [0]
+    n = -(-(size - overlap) // (tile - overlap))
+    if n > TILE_MAX_AXIS:
+        raise ValueError(f"tile_plan: {n} tiles along {axis} ({size} from tiles of {tile} overlapping {overlap}); "
+                         f"at most {TILE_MAX_AXIS}")
+    return tile, [(i * (size - tile)) // (n - 1) for i in range(n)]
+
+
+def tile_plan(H, W, tile, overlap=0):
+    """The sliding-window plan of DESIGN.md §1c for an H x W image: TilePlan(ys, xs, tile, overlap,
+    size), ys / xs the tiles' origins.  Per axis the tile is clipped to the image first, 0 <= overlap
+    < tile is required, the tiles are n = ceil((H - o) / (t - o)) (1 when H == t) with origins
+    (i (H - t)) // (n - 1): every tile inside the image, the first at 0, the last at H - t,
+    neighbours overlapping by at least o.  Tile k = iy * len(xs) + ix (raster order)."""
+    H, W = _pair((H, W), "tile_plan: the image size", 1)
+    th, tw = _pair(tile, "tile_plan: tile", 1)
+    oy, ox = _pair(overlap, "tile_plan: overlap", 0)
+    th, ys = _axis_plan(H, th, oy, "y")
+    tw, xs = _axis_plan(W, tw, ox, "x")
+    return TilePlan(ys, xs, (th, tw), (oy, ox), (H, W))
+
+
+def tile_weights(plan):
+    """(wy [th], wx [tw]) fp64: the blend ramps min(u + 1, t - u, max(1, overlap)) of a tile's rows
+    and columns; a pixel of a tile weighs wy[u] * wx[v]."""
+    out = []
+    for t, o in zip(plan.tile, plan.overlap):
+        u = np.arange(t)
+        out.append(np.minimum(np.minimum(u + 1, t - u), max(1, o)).astype(np.float64))
+    return tuple(out)
+
+
+def check_tile_merge(plan, align, max_depth):
+    """The refusals tile_merge and merge_tiles share."""
+    check_tile_align(align, "align")
+    if align != "none":
+        for n, o, axis in zip((len(plan.ys), len(plan.xs)), plan.overlap, "yx"):
+            if n > 1 and o == 0:
+                raise ValueError(f"align {align!r} fits each tile in its overlap with the tiles before it: the {axis} "
+                                 f"axis has {n} tiles and an overlap of 0")
+    if align == "lstsq_disp" and not (max_depth is not None and max_depth > 0):
+        raise ValueError(f"align 'lstsq_disp' needs max_depth > 0, got {max_depth!r}")
+
+
+def merge_tiles(tiles, plan, align="none", max_depth=None):
+    """Per-tile predictions -> (depth (B,1,H,W) fp32, coef (B,T,4) fp64 or None): the CPU counterpart
+    of mdemi.functional.tile_merge (fp64 throughout, rounded once).  tiles is
+    (B*T,1,th,tw) or (B*T,th,tw), image b's tile k at b*T + k.  "none": the ramp-weighted mean of
+    the covering tiles.  "lstsq" / "lstsq_disp": tile 0 anchors; each later tile k is first fitted
+    (s, t) -- in depth, or in inverse depth -- to the blend of the tiles before it over the pixels
+    they share, coef[b][k] = s, t, n, status; status 1 (s = 1, t = 0) marks a tile that could not
+    be fitted (n < 2, a determinant not finite and > 0, s not > 0).  Under "lstsq_disp" the blend
+    runs in inverse depth and the result is 1 / max(blend, 1 / max_depth)."""
+    check_tile_merge(plan, align, max_depth)
+    tiles = np.asarray(tiles)
+    (th, tw), (H, W) = plan.tile, plan.size
+    T = len(plan.ys) * len(plan.xs)
+    if tiles.ndim == 4 and tiles.shape[1] == 1:
+        tiles = tiles[:, 0]
+    if tiles.ndim != 3 or tiles.shape[1:] != (th, tw) or tiles.shape[0] % T:
+        raise ValueError(f"merge_tiles: tiles must be (B*{T},1,{th},{tw}) or (B*{T},{th},{tw}), got {tiles.shape}")
+    B = tiles.shape[0] // T
+    wy, wx = tile_weights(plan)
+    w = wy[:, None] * wx[None, :]
+    disp = align == "lstsq_disp"
+    out = np.empty((B, 1, H, W), np.float32)
+    coef = None if align == "none" else np.tile(np.array([1.0, 0.0, 0.0, 0.0]), (B, T, 1))
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            num, den = np.zeros((H, W)), np.zeros((H, W))
+            for k in range(T):
+                y0, x0 = plan.ys[k // len(plan.xs)], plan.xs[k % len(plan.xs)]
+                rect = (slice(y0, y0 + th), slice(x0, x0 + tw))
+                p = tiles[b * T + k].astype(np.float64)
+                x = 1.0 / p if disp else p
+                s, t = 1.0, 0.0
+                if align != "none" and k > 0:
+                    y = num[rect] / den[rect]
+                    use = (den[rect] > 0) & np.isfinite(x) & np.isfinite(y)
+                    if disp:
+                        use &= p > 0
+                    xs_, ys_ = x[use], y[use]
+                    n = xs_.size
+                    sx, sy, sxx, sxy = xs_.sum(), ys_.sum(), (xs_ * xs_).sum(), (xs_ * ys_).sum()
+                    det = n * sxx - sx * sx
+                    ok = n >= 2 and np.isfinite(det) and det > 0
+                    if ok:
+                        s, t = float((n * sxy - sx * sy) / det), float((sxx * sy - sx * sxy) / det)
+                        ok = s > 0
+                    if not ok:
+                        s, t = 1.0, 0.0
+                    coef[b, k] = (s, t, n, 0.0 if ok else 1.0)
+                num[rect] += w * (s * x + t if align != "none" else x)
+                den[rect] += w
+            r = num / den
+            if disp:
+                r = 1.0 / np.maximum(r, 1.0 / max_depth)
+            out[b, 0] = r.astype(np.float32)
+    return out, coef
 
 
 def tcompute_errors_gpu(pred, gt, eval_opt, data_type, clamp_pred=True):

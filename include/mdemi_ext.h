@@ -207,6 +207,47 @@ int mdemi_depth_metrics_aligned(const float* pred, const float* gt, int32_t B, i
                                 void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------ */
+/* Scale-invariant boundary F1 (cfg eval.boundary; this framework's own      */
+/* definition, DESIGN.md 1c, after Depth Pro).  Per image, g the ground      */
+/* truth and q the fp32 value the metrics evaluate: pred, or with mode != 0  */
+/* the aligned value mdemi_depth_metrics_aligned forms from coef (read on    */
+/* the device), clamped into [min_depth, max_depth] when clamp_pred != 0.    */
+/* A pair is two horizontally or vertically adjacent pixels both in the      */
+/* valid set V above.  For thresholds t[0] <= ... <= t[n-1], all > 1, a      */
+/* pair is an edge of a map d at t[i] of kind                                */
+/*   0  right is farther   d[y][x+1] > fl32(t[i] d[y][x])                    */
+/*   1  left is farther    d[y][x]   > fl32(t[i] d[y][x+1])                  */
+/*   2  lower is farther   d[y+1][x] > fl32(t[i] d[y][x])                    */
+/*   3  upper is farther   d[y][x]   > fl32(t[i] d[y+1][x])                  */
+/* (one rounded fp32 multiply, a strict compare).  counts [B][n][4][3]       */
+/* (int64, may be NULL) = the pairs that are such an edge in g, in q, in     */
+/* both.  In fp64, in this order:                                            */
+/*   P_i = (sum_k tp / max(pred, 1)) / 4, R_i = (sum_k tp / max(gt, 1)) / 4, */
+/*   F_i = 2 P_i R_i / (P_i + R_i) (0 when P_i + R_i = 0),                   */
+/*   w_i = t[i] / sum t;  f1 = sum w_i F_i, likewise precision and recall.   */
+/* out [B][5] = f1, precision, recall, the number of pairs, status.  An      */
+/* image whose ground truth has no edge at t[0] has no score: status 1,      */
+/* the three scores 0.  Non-finite predictions are outside the contract.     */
+/* thr is read on the host during the call.  The call does not synchronise   */
+/* or allocate; the workspace (mdemi_depth_boundary_workspace_size bytes,    */
+/* 4-byte aligned) is cleared on the stream; integer counters, so two runs   */
+/* give the same bits.  H * W < 2^30, B is 1..65535.  Rows that are 16-byte  */
+/* aligned (W % 4 == 0 and aligned bases) take the 4-pixel vector path.      */
+/* mdemi_depth_boundary_row_chunks: the sweep's grid along the rows.         */
+/* ------------------------------------------------------------------------ */
+#define MDEMI_BOUNDARY_MAX_T 16
+typedef struct mdemi_boundary_thresholds {
+  int32_t n;
+  float t[MDEMI_BOUNDARY_MAX_T];
+} mdemi_boundary_thresholds;
+size_t mdemi_depth_boundary_workspace_size(int32_t B, int32_t n);
+int mdemi_depth_boundary_row_chunks(int32_t H, int32_t W);
+int mdemi_depth_boundary(const float* pred, const float* gt, int32_t B, int32_t H, int32_t W, int32_t y0,
+                         int32_t y1, int32_t x0, int32_t x1, float min_depth, float max_depth, int32_t clamp_pred,
+                         int32_t mode, const double* coef, const mdemi_boundary_thresholds* thr, int64_t* counts,
+                         double* out, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------ */
 /* Flip-eval (config eval.flip_eval): rows of W floats (an NCHW batch is     */
 /* B*C*H rows).  flip_w: y[r][w] = x[r][W-1-w] (out of place).              */
 /* flip_avg_w: y[r][w] = (a[r][w] + b[r][W-1-w]) / 2; y may alias a.        */

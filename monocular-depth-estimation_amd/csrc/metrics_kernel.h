@@ -40,6 +40,13 @@ __device__ __forceinline__ bool met_valid(int64_t p, int W, float g, int y0, int
   const int y = (int)(p / W), x = (int)(p % W);
   return !(y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax));
 }
+// the same test for a caller that has (y, x) already (boundary.hip).  Stated again, not shared:
+// routing met_valid through it reordered the compares of metrics_partial, whose instructions
+// stay the parent's.
+__device__ __forceinline__ bool met_valid_at(int y, int x, float g, int y0, int y1, int x0, int x1, float dmin,
+                                             float dmax) {
+  return !(y < y0 || y >= y1 || x < x0 || x >= x1 || !(g > dmin) || !(g < dmax));
+}
 
 template <int ALIGN, typename... AL>
 __global__ __launch_bounds__(256) void metrics_partial(const float* __restrict__ pred, const float* __restrict__ gt,

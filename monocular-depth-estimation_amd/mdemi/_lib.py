@@ -61,6 +61,7 @@ TelemetryState = _ABI.structs["mdemi_telemetry_state"]
 GuardState = _ABI.structs["mdemi_guard_state"]
 EmaState = _ABI.structs["mdemi_ema_state"]
 AugSample = _ABI.structs["mdemi_aug_sample"]
+BoundaryThresholds = _ABI.structs["mdemi_boundary_thresholds"]
 
 _lib = None
 _lock = threading.Lock()

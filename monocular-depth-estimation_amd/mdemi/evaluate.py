@@ -19,6 +19,9 @@ of the driver itself is unpinned; each helper is pinned by its own tests):
   DESIGN.md 1c): pred is first aligned per image to its ground truth
   eval.tile (this framework's own key): pred comes from a
   TiledPredictor -- the model run on overlapping tiles, the tiles blended
+  eval.boundary (this framework's own key): each image's
+  scale-invariant boundary F1, precision and recall of the evaluated value
+  (mdemi_depth_boundary) are reported next to the nine metrics
 
 Every step is a libmdemi launch (flip: mdemi_flip_w / mdemi_flip_avg_w;
 resize: mdemi_bilinear_*; metrics: mdemi_depth_metrics, or mdemi_depth_align +
@@ -33,7 +36,7 @@ from .utils.common_utils import RunningAverageDict
 from .utils.depth_utils import tcompute_errors_gpu
 from .utils.dist_utils import all_reduce_dict
 
-__all__ = ["predict_depth", "evaluate_batch", "evaluate", "GraphedPredictor", "TiledPredictor"]
+__all__ = ["predict_depth", "evaluate_batch", "evaluate", "MetricMeans", "GraphedPredictor", "TiledPredictor"]
 
 
 def _depth_of(out):
@@ -189,6 +192,50 @@ class TiledPredictor:
         return depth
 
 
+class MetricMeans:
+    """The means evaluate() returns, from per-image metric dicts: the nine metrics exactly as the
+    reference's RunningAverageDict and all_reduce_dict make them, and -- with boundary=True (cfg
+    eval.boundary) -- the boundary scores beside them with a sum and a count of their own, since an
+    image without a boundary score (no BOUNDARY_KEYS in its dict) counts in the nine and not there."""
+
+    def __init__(self, boundary=False):
+        from .utils.depth_utils import BOUNDARY_KEYS
+        self.boundary, self.keys = bool(boundary), BOUNDARY_KEYS
+        self.avg, self.n = RunningAverageDict(), 0
+        self.edge_sum, self.edge_n = {k: 0.0 for k in BOUNDARY_KEYS}, 0
+
+    def update(self, m):
+        if all(k in m for k in self.keys):
+            for k in self.keys:
+                self.edge_sum[k] += float(m[k])
+            self.edge_n += 1
+        self.avg.update({k: v for k, v in m.items() if k not in self.keys})
+        self.n += 1
+
+    def result(self, weight_by_count=False):
+        """The nine means (the unweighted rank mean, or the (sum, count) reduction under
+        weight_by_count), then under boundary the three boundary means -- always reduced across
+        ranks as (sum, count); absent when no image on any rank had a score -- and boundary_images,
+        the number of images that had one.  Every rank makes the same collective calls."""
+        if not weight_by_count:
+            out = all_reduce_dict(self.avg.get_value(), op="mean")
+        else:
+            from .utils.depth_utils import METRICS
+            n = self.n
+            vals = self.avg.get_value() if n else {k: 0.0 for k in METRICS}  # every rank reduces the same keys
+            sums = {k: float(v) * n for k, v in vals.items()}
+            tot = all_reduce_dict({"__count": float(n), **sums}, op="sum")
+            count = tot.pop("__count")
+            out = {k: v / count for k, v in tot.items()}
+        if self.boundary:
+            tot = all_reduce_dict({"__count": float(self.edge_n), **self.edge_sum}, op="sum")
+            count = int(round(float(tot.pop("__count"))))
+            if count:
+                out.update({k: float(v) / count for k, v in tot.items()})
+            out["boundary_images"] = count
+        return out
+
+
 def evaluate(model, batches, eval_opt, data_type, weight_by_count=False):
     """Running mean of the metrics over (img, gt) batches on this rank, then the mean over ranks
     (all_reduce_dict op="mean"; a pass-through without a process group).
@@ -196,23 +243,18 @@ def evaluate(model, batches, eval_opt, data_type, weight_by_count=False):
     The rank mean is unweighted, as all_reduce_dict(op="mean") makes it: exact when every
     rank sees the same number of images (a padded DistributedSampler).  weight_by_count=True
     instead reduces (sum, count) per metric and divides once -- the exact dataset mean when
-    ranks see different numbers of images (uneven last batch, no padding)."""
+    ranks see different numbers of images (uneven last batch, no padding).
+
+    With eval.boundary the result also carries the boundary scores, each the mean over the images
+    that have one (MetricMeans), and boundary_images, their number."""
+    from .utils.depth_utils import check_boundary
     was_training = model.training
     model.eval()
-    avg = RunningAverageDict()
-    n = 0
+    means = MetricMeans(boundary=check_boundary(eval_opt.get("boundary")) is not None)
     try:
         for img, gt in batches:
             for m in evaluate_batch(model, img, gt, eval_opt, data_type):
-                avg.update(m)
-                n += 1
+                means.update(m)
     finally:
         model.train(was_training)
-    if not weight_by_count:
-        return all_reduce_dict(avg.get_value(), op="mean")
-    from .utils.depth_utils import METRICS
-    vals = avg.get_value() if n else {k: 0.0 for k in METRICS}  # every rank reduces the same keys
-    sums = {k: float(v) * n for k, v in vals.items()}
-    tot = all_reduce_dict({"__count": float(n), **sums}, op="sum")
-    count = tot.pop("__count")
-    return {k: v / count for k, v in tot.items()}
+    return means.result(weight_by_count)

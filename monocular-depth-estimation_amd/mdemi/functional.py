@@ -2180,16 +2180,18 @@ def depth_align(pred, gt, rect, min_depth, max_depth, mode):
     return coef
 
 
-def depth_metrics(pred, gt, rect, min_depth, max_depth, clamp_pred=True, align=None, return_aligned=False):
+def depth_metrics(pred, gt, rect, min_depth, max_depth, clamp_pred=True, align=None, return_aligned=False,
+                  coef=None):
     """Per-image [a1, a2, a3, abs_rel, sq_rel, rmse, rmse_log, silog, log_10, n_valid] (fp64) over
     crop rect (y0, y1, x0, x1) & min_depth < gt < max_depth (utils/depth_utils.py:4-54).
 
     align ("median", "lstsq", "lstsq_disp"): the metrics of the prediction aligned per image
     (depth_align), rows of 12: the ten columns, then s and t.  return_aligned=True also returns
-    the aligned prediction, shaped as pred, before the clamp."""
+    the aligned prediction, shaped as pred, before the clamp.  coef: depth_align's rows for these
+    very tensors and this mode, when the caller has them already."""
     if align is None:
-        if return_aligned:
-            raise ValueError("return_aligned needs an align mode")
+        if return_aligned or coef is not None:
+            raise ValueError("return_aligned and coef need an align mode")
         _require_cuda(pred, gt)
         pred, gt = _c(pred), _c(gt)
         b = pred.shape[0]
@@ -2204,8 +2206,8 @@ def depth_metrics(pred, gt, rect, min_depth, max_depth, clamp_pred=True, align=N
         return out
     code = _align_code(align)
     pred, gt = _c(pred), _c(gt)
-    coef = depth_align(pred, gt, rect, min_depth, max_depth, align)
     b = pred.shape[0]
+    coef = depth_align(pred, gt, rect, min_depth, max_depth, align) if coef is None else _align_coef(coef, b)
     h, w = pred.shape[-2:]
     out = torch.empty(b, 12, device=pred.device, dtype=torch.float64)
     aligned = torch.empty_like(pred) if return_aligned else None
@@ -2217,6 +2219,51 @@ def depth_metrics(pred, gt, rect, min_depth, max_depth, clamp_pred=True, align=N
                                             float(max_depth), int(clamp_pred), code, coef.data_ptr(), L.ptr(aligned),
                                             out.data_ptr(), ws.data_ptr(), L.stream()), "depth_metrics_aligned")
     return (out, aligned) if return_aligned else out
+
+
+def _align_coef(coef, b):
+    if coef.shape != (b, 4) or coef.dtype != torch.float64 or not coef.is_cuda:
+        raise ValueError(f"coef must be depth_align's ({b}, 4) fp64 rows on the GPU, got {tuple(coef.shape)} "
+                         f"{coef.dtype}")
+    return _c(coef)
+
+
+def depth_boundary(pred, gt, rect, min_depth, max_depth, clamp_pred=True, align=None, thresholds=None,
+                   return_counts=False, coef=None):
+    """Per-image scale-invariant boundary F1: (B, 5) fp64 rows [f1, precision,
+    recall, n_pairs, status] over the pairs of adjacent pixels that are both in crop rect &
+    min_depth < gt < max_depth.  It scores the value depth_metrics evaluates: pred, aligned per
+    image first under align ("median", "lstsq", "lstsq_disp"; one depth_align call, or the caller's
+    coef), clamped into [min_depth, max_depth] when clamp_pred.  thresholds: 1..16 fp32 depth
+    ratios above 1, non-decreasing (default utils.depth_utils.boundary_thresholds()).  status 1
+    marks an image without a score (its ground truth has no edge at the lowest threshold; the
+    three scores are 0).  return_counts=True also returns the (B, n, 4, 3) int64 edge counts:
+    per threshold and kind (right, left, lower, upper is farther), in gt, in pred, in both."""
+    import numpy as np
+    from .utils.depth_utils import _thresholds32, boundary_thresholds
+    t = boundary_thresholds() if thresholds is None else _thresholds32(thresholds)
+    code = 0 if align is None else _align_code(align)
+    if code == 0 and coef is not None:
+        raise ValueError("coef needs an align mode")
+    _require_cuda(pred, gt)
+    pred, gt = _c(pred), _c(gt)
+    b = pred.shape[0]
+    h, w = pred.shape[-2:]
+    if code:
+        coef = depth_align(pred, gt, rect, min_depth, max_depth, align) if coef is None else _align_coef(coef, b)
+    n = int(t.size)
+    thr = L.BoundaryThresholds(n=n)
+    thr.t[:n] = np.asarray(t, np.float32).tolist()
+    out = torch.empty(b, 5, device=pred.device, dtype=torch.float64)
+    counts = torch.empty(b, n, 4, 3, device=pred.device, dtype=torch.int64) if return_counts else None
+    lib = L.load()
+    # the same slot as depth_align's and depth_metrics': stream order puts this call after their last read of it
+    ws = _ws(lib.mdemi_depth_boundary_workspace_size(b, n), pred.device, slot=3)
+    y0, y1, x0, x1 = rect
+    L.check(lib.mdemi_depth_boundary(pred.data_ptr(), gt.data_ptr(), b, h, w, y0, y1, x0, x1, float(min_depth),
+                                     float(max_depth), int(clamp_pred), code, L.ptr(coef), ctypes.addressof(thr),
+                                     L.ptr(counts), out.data_ptr(), ws.data_ptr(), L.stream()), "depth_boundary")
+    return (out, counts) if return_counts else out
 
 
 def conv_weight_layout(w, mode, conv_shape=None):

@@ -58,6 +58,9 @@ def _args(argv):
                          "the tile)")
     ap.add_argument("--tile-align", default=None, choices=["none", "lstsq", "lstsq_disp"],
                     help="override eval.tile_align: fit each tile's scale and shift to the tiles before it")
+    ap.add_argument("--boundary", action="store_true",
+                    help="set the config's eval.boundary: report the scale-invariant boundary F1, precision and "
+                         "recall of the depth edges next to the nine metrics (validation and --test)")
     ap.add_argument("--ema", action="store_true",
                     help="with --test: evaluate the checkpoint's averaged weights (ema_state_dict)")
     ap.add_argument("--max-steps", type=int, default=None, help="stop after this many optimizer steps (in all)")
@@ -76,6 +79,8 @@ def _override(opt, args):
         opt.setdefault("loss", {})["ssi_weight"] = args.ssi_weight
     if args.align is not None:
         opt.setdefault("eval", {})["align"] = args.align
+    if args.boundary:
+        opt.setdefault("eval", {})["boundary"] = True
     tile_overrides(opt, args)
     return opt
 
@@ -139,7 +144,8 @@ def main(argv=None) -> int:
 
     # 1. the config
     opt = _override(parse(args.opt, write_option=rank == 0 and not args.test), args)
-    from .train.builder import eval_align, eval_tile, grad_match_config, nonfinite_policy, ssi_config
+    from .train.builder import (eval_align, eval_boundary, eval_record, eval_tile, grad_match_config, nonfinite_policy,
+                                ssi_config)
     from .train.ema import ema_config
     nonfinite_policy(opt)  # a bad train.nonfinite / max_consecutive_skips fails here, before any worker starts
     ema_config(opt)  # and so does a bad train.ema_decay / ema_warmup / ema_validate
@@ -147,6 +153,7 @@ def main(argv=None) -> int:
     ssi_config(opt)  # and a bad loss.ssi_weight / ssi_space / ssi_trim / ssi_norm
     align = eval_align(opt)  # and a bad eval.align
     tile = eval_tile(opt)  # and a bad eval.tile / tile_overlap / tile_align / tile_batch
+    boundary = eval_boundary(opt)  # and a bad eval.boundary
     if args.ema and not args.test:
         raise SystemExit("mdemi.run --ema selects the weights --test evaluates; to train with averaged weights set "
                          "train.ema_decay (or --ema-decay)")
@@ -219,8 +226,8 @@ def main(argv=None) -> int:
             model = build_model(opt, drop_path=0.0)
             _load_weights(model, ck_path, ema=args.ema)
             model.to(dev).eval()
-            metrics = {k: float(v) for k, v in evaluate(predictor(model), test_batches(), eval_opt, data_type,
-                                                        weight_by_count=True).items()}
+            metrics = eval_record(evaluate(predictor(model), test_batches(), eval_opt, data_type, weight_by_count=True),
+                                  boundary)
             rec = {"type": "test", "checkpoint": ck_path, **metrics}
             if args.ema:
                 rec["weights"] = "ema"

@@ -239,6 +239,26 @@ def eval_align(opt):
     return check_align_mode(opt.get("eval", {}).get("align", "none"))
 
 
+def eval_boundary(opt):
+    """eval.boundary, validated: None when the key is absent or false; true -> the defaults
+    (1.05, 1.25, 10); {"t_min": .., "t_max": .., "n": ..} -> (t_min, t_max, n), the range and
+    number of depth-ratio thresholds of the boundary F1 the evaluator reports next to the nine
+    metrics.  Unknown keys, t_min <= 1, t_max < t_min, n outside 1..16 and
+    booleans as numbers raise a ValueError that names the key."""
+    from ..utils.depth_utils import check_boundary
+    return check_boundary(opt.get("eval", {}).get("boundary"))
+
+
+def eval_record(metrics, boundary):
+    """evaluate()'s result as the fields of a "valid" / "test" record: floats, boundary_images an
+    integer, and under eval.boundary "boundary": [t_min, t_max, n]."""
+    rec = {k: float(v) for k, v in metrics.items()}
+    if boundary is not None:
+        rec["boundary_images"] = int(rec.get("boundary_images", 0))
+        rec["boundary"] = list(boundary)
+    return rec
+
+
 TILE_KEYS = ("tile", "tile_overlap", "tile_align", "tile_batch")
 
 

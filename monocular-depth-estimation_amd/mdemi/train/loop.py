@@ -33,7 +33,8 @@ import torch
 
 from .. import _lib as L
 from ..utils.dist_utils import all_reduce_dict
-from .builder import eval_align, eval_tile, nonfinite_policy, optimizer_steps_per_epoch
+from .builder import (eval_align, eval_boundary, eval_record, eval_tile, nonfinite_policy,
+                      optimizer_steps_per_epoch)
 from .ema import ema_config
 from .telemetry import NonFiniteStep
 
@@ -154,7 +155,10 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     a second record with "weights": "model".  With eval.align other than "none" the caller's
     validate() reports aligned metrics; the record then carries "align": MODE and best.pth is
     chosen on the aligned abs_rel.  With eval.tile the caller's validate() predicts in tiles and the
-    record carries "tile": [h, w] and "tile_align".  telemetry defaults to
+    record carries "tile": [h, w] and "tile_align".  With eval.boundary it reports the boundary
+    scores too; the records (the raw weights' one under "both" included) then carry them,
+    "boundary_images" and "boundary": [t_min, t_max, n]; best.pth is still chosen on abs_rel.
+    telemetry defaults to
     trainer.telemetry.  ``best`` is (abs_rel, epoch, iter) of the best checkpoint so far
     (a resumed run).  Rank 0 writes out_dir/log.jsonl -- {"type": "train", ...} every
     train.print_freq steps, {"type": "valid", ...} per validation -- and latest.pth /
@@ -184,6 +188,7 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
     policy, max_skips = nonfinite_policy(opt)
     align = eval_align(opt)
     tile = eval_tile(opt)
+    boundary = eval_boundary(opt)
     skip_mode = policy == "skip"
     guard = getattr(trainer.optimizer, "skipped_steps", None) if skip_mode else None
     if skip_mode and (guard is None or not getattr(trainer.optimizer, "skip_nonfinite", True)):
@@ -300,12 +305,12 @@ def fit(trainer, train_batches, validate, opt, out_dir, *, telemetry=None, steps
             require_finite_model()
         raw = None
         if ema is None:
-            metrics = {k: float(v) for k, v in validate().items()}
+            metrics = eval_record(validate(), boundary)
         else:  # the averaged weights under the live model's current buffers
             ema.sync_buffers(trainer.model)
-            metrics = {k: float(v) for k, v in validate(ema.module).items()}
+            metrics = eval_record(validate(ema.module), boundary)
             if ema_validate == "both":
-                raw = {k: float(v) for k, v in validate(trainer.model).items()}
+                raw = eval_record(validate(trainer.model), boundary)
         if hasattr(trainer, "train_mode"):
             trainer.train_mode()  # evaluate() restores model.train(); frozen BatchNorms go back to eval
         improved = metrics["abs_rel"] < best_value

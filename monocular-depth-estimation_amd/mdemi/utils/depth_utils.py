@@ -8,20 +8,25 @@ aligns each prediction to its ground truth first (median scaling, or least-squar
 shift in depth or in inverse depth): on the GPU inside `tcompute_errors_gpu`
 (mdemi_depth_align + mdemi_depth_metrics_aligned), on the CPU with `align_depth`.  cfg eval.tile
 predicts in overlapping tiles: `tile_plan` lays them out and `merge_tiles` is the CPU counterpart
-of the GPU merge (mdemi.functional.tile_merge)."""
+of the GPU merge (mdemi.functional.tile_merge).  cfg eval.boundary adds the scale-invariant boundary
+F1 of each image (mdemi_depth_boundary; `boundary_counts` and `boundary_f1` are its numpy counterpart)."""
 from collections import namedtuple
 
 import numpy as np
 
 __all__ = ["cal_eval_mask", "tcompute_errors", "eval_crop_rect", "tcompute_errors_gpu", "METRICS", "ALIGN_MODES",
            "check_align_mode", "align_depth", "TILE_ALIGN_MODES", "TILE_MAX_AXIS", "TilePlan", "check_tile_align",
-           "tile_plan", "tile_weights", "check_tile_merge", "merge_tiles"]
+           "tile_plan", "tile_weights", "check_tile_merge", "merge_tiles", "BOUNDARY_KEYS", "BOUNDARY_MAX_T",
+           "BOUNDARY_DEFAULTS", "check_boundary", "boundary_thresholds", "boundary_counts", "boundary_f1"]
 
 METRICS = ("a1", "a2", "a3", "abs_rel", "sq_rel", "rmse", "rmse_log", "silog", "log_10")
 ALIGN_MODES = ("none", "median", "lstsq", "lstsq_disp")
 TILE_ALIGN_MODES = ("none", "lstsq", "lstsq_disp")
 TILE_MAX_AXIS = 32  # MDEMI_TILE_MAX_AXIS
 TilePlan = namedtuple("TilePlan", "ys xs tile overlap size")
+BOUNDARY_KEYS = ("boundary_f1", "boundary_precision", "boundary_recall")
+BOUNDARY_MAX_T = 16  # MDEMI_BOUNDARY_MAX_T
+BOUNDARY_DEFAULTS = {"t_min": 1.05, "t_max": 1.25, "n": 10}
 
 
 def check_align_mode(mode, what="eval.align"):
@@ -217,15 +222,129 @@ def merge_tiles(tiles, plan, align="none", max_depth=None):
     return out, coef
 
 
+def _number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_boundary(spec, what="eval.boundary"):
+    """eval.boundary, validated: None when it is absent (None) or False; True -> the defaults
+    (1.05, 1.25, 10); {"t_min", "t_max", "n"} (each optional) -> (t_min, t_max, n) with
+    1 < t_min <= t_max and 1 <= n <= 16.  Anything else raises a ValueError naming the key."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        spec = {}
+    if not isinstance(spec, dict):
+        raise ValueError(f"{what} must be true, false or an object with t_min / t_max / n, got {spec!r}")
+    unknown = [k for k in spec if k not in BOUNDARY_DEFAULTS]
+    if unknown:
+        raise ValueError(f"{what}.{unknown[0]} is not a key of {what}: it takes {tuple(BOUNDARY_DEFAULTS)}")
+    v = {**BOUNDARY_DEFAULTS, **spec}
+    t_min, t_max, n = v["t_min"], v["t_max"], v["n"]
+    if not (_number(t_min) and np.isfinite(t_min) and t_min > 1):
+        raise ValueError(f"{what}.t_min must be a number above 1, got {t_min!r}")
+    if not (_number(t_max) and np.isfinite(t_max) and t_max >= t_min):
+        raise ValueError(f"{what}.t_max must be a number not below t_min = {t_min!r}, got {t_max!r}")
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= n <= BOUNDARY_MAX_T:
+        raise ValueError(f"{what}.n must be an integer in 1..{BOUNDARY_MAX_T}, got {n!r}")
+    return float(t_min), float(t_max), int(n)
+
+
+def boundary_thresholds(t_min=1.05, t_max=1.25, n=10):
+    """The n thresholds of DESIGN.md §1c: np.linspace(t_min, t_max, n) rounded to fp32."""
+    t_min, t_max, n = check_boundary({"t_min": t_min, "t_max": t_max, "n": n}, "boundary_thresholds")
+    t = np.linspace(t_min, t_max, n).astype(np.float32)
+    if not (t[0] > 1 and np.all(np.diff(t) >= 0)):
+        raise ValueError(f"boundary_thresholds: t_min = {t_min!r} rounds to 1 in fp32")
+    return t
+
+
+def _thresholds32(thresholds):
+    t = np.asarray(thresholds)
+    if t.dtype != np.float32 or t.ndim != 1 or not 1 <= t.size <= BOUNDARY_MAX_T:
+        raise ValueError(f"thresholds must be 1..{BOUNDARY_MAX_T} float32 values (boundary_thresholds), got {t!r}")
+    if not (np.all(np.isfinite(t)) and t[0] > 1 and np.all(np.diff(t) >= 0)):
+        raise ValueError(f"thresholds must be finite, above 1 and non-decreasing, got {t!r}")
+    return t
+
+
+def boundary_counts(gt, pred, valid, thresholds):
+    """The edge counts of DESIGN.md §1c on 2-D maps, the CPU counterpart of mdemi_depth_boundary:
+    (n, 4, 3) int64 = per threshold and kind (right, left, lower, upper is farther) the pairs of
+    adjacent valid pixels that are an edge in gt, in pred and in both.  pred is the evaluated value
+    (aligned and clamped already); every compare is fp32: b > fl32(tau a)."""
+    t = _thresholds32(thresholds)
+    g, q, v = np.asarray(gt, np.float32), np.asarray(pred, np.float32), np.asarray(valid, bool)
+    if g.ndim != 2 or q.shape != g.shape or v.shape != g.shape:
+        raise ValueError(f"boundary_counts: gt, pred and valid must be 2-D maps of one shape, got {g.shape}, "
+                         f"{q.shape}, {v.shape}")
+    out = np.zeros((t.size, 4, 3), np.int64)
+    with np.errstate(all="ignore"):
+        for d, (a, b) in enumerate(((np.s_[:, :-1], np.s_[:, 1:]), (np.s_[:-1, :], np.s_[1:, :]))):
+            both = v[a] & v[b]
+            for i, tau in enumerate(t):
+                for k, (lo, hi) in enumerate(((a, b), (b, a))):
+                    eg = both & (g[hi] > tau * g[lo])
+                    eq = both & (q[hi] > tau * q[lo])
+                    out[i, 2 * d + k] = eg.sum(), eq.sum(), (eg & eq).sum()
+    return out
+
+
+def boundary_f1(counts, thresholds):
+    """Counts (n, 4, 3) -> {"boundary_f1", "boundary_precision", "boundary_recall"} in fp64, or None
+    for an image whose ground truth has no edge at the lowest threshold: per
+    threshold P = mean over the kinds of tp / max(pred, 1), R the same over gt, F their harmonic
+    mean (0 when both are 0); the scores are the means over the thresholds weighted by tau."""
+    t = _thresholds32(thresholds).astype(np.float64)
+    c = np.asarray(counts)
+    if c.shape != (t.size, 4, 3):
+        raise ValueError(f"boundary_f1: counts must be ({t.size}, 4, 3), got {c.shape}")
+    if int(c[0, :, 0].sum()) == 0:
+        return None
+    tsum = 0.0
+    for tau in t:
+        tsum += float(tau)
+    f1 = prec = rec = 0.0
+    for i in range(t.size):
+        p = r = 0.0
+        for k in range(4):
+            n_gt, n_pr, n_tp = (int(x) for x in c[i, k])
+            p += n_tp / max(n_pr, 1)
+            r += n_tp / max(n_gt, 1)
+        p *= 0.25
+        r *= 0.25
+        f = 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+        w = float(t[i]) / tsum
+        f1 += w * f
+        prec += w * p
+        rec += w * r
+    return dict(zip(BOUNDARY_KEYS, (f1, prec, rec)))
+
+
 def tcompute_errors_gpu(pred, gt, eval_opt, data_type, clamp_pred=True):
     """Per-image metrics for a batch on the GPU: pred/gt (B, 1, H, W) fp32 CUDA tensors; valid =
     crop & min_depth_eval < gt < max_depth_eval (cfg eval.*).  Returns a list of dicts (one per
     image, the reference's keys) -- feed them to RunningAverageDict / all_reduce_dict.  With
-    eval.align other than "none" they are the metrics of the per-image aligned prediction."""
+    eval.align other than "none" they are the metrics of the per-image aligned prediction.  With
+    eval.boundary each dict also carries BOUNDARY_KEYS, the boundary scores of the same evaluated
+    value -- except for an image that has no score (no ground-truth edge), which carries none."""
     from .. import functional as mf
     h, w = gt.shape[-2:]
     rect = eval_crop_rect(eval_opt, h, w, data_type)
     align = check_align_mode(eval_opt.get("align", "none"))
-    out = mf.depth_metrics(pred, gt, rect, eval_opt["min_depth_eval"], eval_opt["max_depth_eval"],
-                           clamp_pred=clamp_pred, align=None if align == "none" else align).cpu().numpy()
-    return [dict(zip(METRICS, row[:9].tolist())) for row in out]
+    boundary = check_boundary(eval_opt.get("boundary"))
+    align = None if align == "none" else align
+    dmin, dmax = eval_opt["min_depth_eval"], eval_opt["max_depth_eval"]
+    if boundary is None:
+        out = mf.depth_metrics(pred, gt, rect, dmin, dmax, clamp_pred=clamp_pred, align=align)
+        return [dict(zip(METRICS, row[:9].tolist())) for row in out.cpu().numpy()]
+    # one alignment serves both: the metrics and the edges are those of the same q
+    coef = None if align is None else mf.depth_align(pred, gt, rect, dmin, dmax, align)
+    out = mf.depth_metrics(pred, gt, rect, dmin, dmax, clamp_pred=clamp_pred, align=align, coef=coef)
+    edge = mf.depth_boundary(pred, gt, rect, dmin, dmax, clamp_pred=clamp_pred, align=align, coef=coef,
+                             thresholds=boundary_thresholds(*boundary)).cpu().numpy()
+    rows = [dict(zip(METRICS, row[:9].tolist())) for row in out.cpu().numpy()]
+    for row, e in zip(rows, edge):
+        if e[4] == 0:
+            row.update(zip(BOUNDARY_KEYS, e[:3].tolist()))
+    return rows
